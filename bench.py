@@ -16,6 +16,10 @@ work is fixed as N grows -> strong scaling.
 Strategy "direct" (config 5, or --strategy direct): a step = `--users-per-step` users per GPU,
 each user's catalog scored against its whole history by the fused kernel (nais_score_catalog) +
 top-50; users sharded across ranks by LPT, tables replicated (RCCL broadcast) -> weak scaling.
+
+A plain run sets up, warms up, times `--steps` steps and prints the result line; `--full` adds the
+secondary legs, the oracle self-checks and the CPU baseline after the timed steps;
+`--dump-outputs DIR` writes the last timed step's top-k ids and scores as DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -68,6 +72,14 @@ def parse():
     ap.add_argument("--h-max", type=int, default=200)
     ap.add_argument("--topk", type=int, default=50)
     ap.add_argument("--precision", default="fp16x6", choices=sorted(PRODUCTS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the "
+                         "exact-gather, fp32, fp16x3, prior and region_distance legs, the history-gather "
+                         "and training-step legs, the oracle self-checks and the CPU baseline (each can "
+                         "still be switched off with its --no-* option); a plain run skips them all")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (ids, scores) as "
+                         "DIR/<name>.npy; a fixed seeded sample of the rows when more than 64 MB")
     ap.add_argument("--no-fp32-leg", action="store_true",
                     help="skip the secondary legs (fp32_path, fp16x3_path, prior_path, region_distance_path)")
     ap.add_argument("--leg-steps", type=int, default=3, help="timed steps of each secondary leg")
@@ -94,7 +106,35 @@ def parse():
     ap.add_argument("--strategy", default="auto", choices=["auto", "pairs", "direct"],
                     help="auto: pairs for config 4 (each (item, candidate) pair shared by ~50 users), "
                          "direct for config 5's 4096-user subset (sharing ~1)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:   # a plain run: set up, warm up, time the steps, print the line
+        a.no_fp32_leg = a.no_cpu_baseline = a.no_gather_leg = a.no_train_leg = a.no_self_check = True
+    return a
+
+
+DUMP_BYTES = 64 * 1000 * 1000 - 4096   # the budget of a dump's array data (the rest: .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: `arrays` = {name: [rows, ...] array} of the last timed step's results, one
+    DIR/<name>.npy each in float32 (float64 where float32 would not hold the values exactly:
+    integer ids from 2^24). Over DUMP_BYTES in all, every array keeps the same seeded sample of
+    its rows (sorted), so two builds dump the same rows."""
+    os.makedirs(dirname, exist_ok=True)
+    out = {}
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        wide = arr.dtype == np.float64 or (arr.dtype.kind in "iu" and arr.size and int(np.abs(arr).max()) >= 1 << 24)
+        out[name] = arr.astype(np.float64 if wide else np.float32)
+    rows = min(len(v) for v in out.values())
+    per_row = sum(v[:rows].nbytes for v in out.values()) / max(1, rows)
+    sel = None
+    if per_row * rows > DUMP_BYTES:   # the sampled row numbers are dumped too (8 B per row)
+        keep = int(DUMP_BYTES // (per_row + 8))
+        sel = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        out["sample_rows"] = np.arange(rows, dtype=np.float64)
+    for name, v in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v[:rows][sel] if sel is not None else v))
 
 
 def cpu_threads():
@@ -629,6 +669,9 @@ def main():
     elapsed, score_ms, topk_ms = run(a.precision, a.warmup, a.steps)
     pairs = sum(steps[a.warmup + i][1] for i in range(a.steps))
     work = sum(steps[a.warmup + i][2] for i in range(a.steps))
+    if a.dump_outputs and rank == 0:   # the last timed step's lists (N > 1: every rank's, gathered)
+        dump_outputs(a.dump_outputs, {"topk_ids": (gat_ids if world > 1 else ids).cpu().numpy(),
+                                      "topk_scores": (gat_sc if world > 1 else top).cpu().numpy()})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -804,6 +847,9 @@ def bench_pairs(a, model, csr, data, hist_len, p_host, dev, rank, world, dist):
     elapsed, per = run(a.precision, a.warmup, a.steps)
     wall_ms = last["wall_ms"]
     head_out = last["out"]   # the legs below overwrite last["out"]
+    if a.dump_outputs and rank == 0:   # the last timed job's [users, k] lists (N > 1: the merged ones)
+        dump_outputs(a.dump_outputs, {"topk_ids": head_out[0].cpu().numpy(),
+                                      "topk_scores": head_out[1].cpu().numpy()})
     ranks = None
     if world > 1:   # every rank's phase busy times (ms per step), gathered over the same group
         ph = ("table", "gather", "allgather", "merge", "topk")
@@ -940,7 +986,7 @@ def bench_pairs(a, model, csr, data, hist_len, p_host, dev, rank, world, dist):
     dominant["other_kernel"] = other
     dominant["topk_ms_per_step"] = k_ms
     legs = {}
-    if world == 1 and per.get("bounded"):
+    if a.full and world == 1 and per.get("bounded"):
         # the same job on the exact fused gather (float tables, 8 B per history entry and column):
         # its time, and the headline's lists against it -- the same ids and score bits
         catalog.PAIR_BOUNDED = False

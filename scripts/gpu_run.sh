@@ -1,8 +1,8 @@
 #!/bin/bash
 # The one GPU-box runner (via gpurun): scripts/gpu_run.sh <mode> <tag> [extra args]
-#   check     the GPU suite, smoke(), the default bench line
+#   check     the GPU suite, smoke(), the bench line with every leg (bench.py --full)
 #   tests     the GPU suite only (extra args replace the selection, e.g. test files, -k EXPR)
-#   bench     the default bench line (extra args go to bench.py)
+#   bench     the bench line with every leg (bench.py --full; extra args go to bench.py)
 #   profile   rocprofv3 kernel trace + FETCH_SIZE / WRITE_SIZE passes of the bench command
 #   pmc       SQ counter passes of the standalone pair-table block (scripts/bench_table.py; extra
 #             args go to bench_table.py, e.g. --dim 128 --hidden 128)
@@ -35,12 +35,12 @@ case "$mode" in
   check)
     tests || exit $?
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -20 $out/smoke.log; exit 1; }
-    timeout -k 10 600 python bench.py "$@" > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+    timeout -k 10 600 python bench.py --full "$@" > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
     line $out/bench.json ;;
   tests)
     tests "$@" ;;
   bench)
-    timeout -k 10 900 python bench.py "$@" > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
+    timeout -k 10 900 python bench.py --full "$@" > $out/bench.json 2> $out/bench.err || { tail -20 $out/bench.err; exit 1; }
     line $out/bench.json ;;
   profile)
     scripts/gpu_profile.sh "$tag" --no-train-leg --steps 5 --warmup 1 "$@" ;;
@@ -50,9 +50,9 @@ case "$mode" in
     timeout -k 10 600 scripts/gpu_pmc_cmd.sh ${tag}_pmc x6n_kernel scripts/bench_table.py --blocks 8 --rounds 1 "$@" > $out/pmc.txt 2>&1 || { tail -5 $out/pmc.txt; exit 1; }
     tail -20 $out/pmc.txt ;;
   configs)
-    timeout -k 10 400 python bench.py --config 2 --no-fp32-leg --no-gather-leg --no-train-leg --steps 5 --warmup 2 --cpu-users 16 --cpu-seconds 20 > $out/config2.json 2> $out/config2.err || { tail -20 $out/config2.err; exit 1; }
+    timeout -k 10 400 python bench.py --config 2 --full --no-fp32-leg --no-gather-leg --no-train-leg --steps 5 --warmup 2 --cpu-users 16 --cpu-seconds 20 > $out/config2.json 2> $out/config2.err || { tail -20 $out/config2.err; exit 1; }
     line $out/config2.json
-    timeout -k 10 500 python bench.py --config 5 --no-fp32-leg --no-gather-leg --no-train-leg > $out/config5_direct.json 2> $out/config5_direct.err || { tail -20 $out/config5_direct.err; exit 1; }
+    timeout -k 10 500 python bench.py --config 5 --full --no-fp32-leg --no-gather-leg --no-train-leg > $out/config5_direct.json 2> $out/config5_direct.err || { tail -20 $out/config5_direct.err; exit 1; }
     line $out/config5_direct.json
     timeout -k 10 600 python bench.py --config 5 --strategy pairs --emulate-world 8 --no-fp32-leg --no-gather-leg --no-train-leg --no-self-check --steps 1 --warmup 1 > $out/config5_pairs_shard8.json 2> $out/config5_pairs_shard8.err || { tail -20 $out/config5_pairs_shard8.err; exit 1; }
     line $out/config5_pairs_shard8.json ;;
@@ -74,7 +74,7 @@ case "$mode" in
         > $out/n$N.json 2> $out/n$N.err || { tail -20 $out/n$N.err; exit 1; }
       line $out/n$N.json
     done
-    timeout -k 10 400 python bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --no-fp32-leg --no-gather-leg --no-train-leg --no-cpu-baseline \
+    timeout -k 10 400 python bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --full --no-fp32-leg --no-gather-leg --no-train-leg --no-cpu-baseline \
       > $out/rank2_gloo.json 2> $out/rank2_gloo.err || { tail -20 $out/rank2_gloo.err; exit 1; }
     line $out/rank2_gloo.json ;;
   *)

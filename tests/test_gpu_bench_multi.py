@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_gloo_one_json_line():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
            "--num-users", "2000", "--num-pois", "20000", "--steps", "3", "--warmup", "1",
+           "--full",   # the self_check asserted below is not part of a plain run
            "--no-fp32-leg", "--no-gather-leg", "--no-train-leg", "--no-cpu-baseline"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
