@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 14   /* 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 15   /* 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -316,6 +316,63 @@ int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
                               const int32_t* surv_count, int32_t surv_cap, const uint64_t* tau,
                               uint64_t* keys, int32_t* kcount, int32_t* nan_count, int32_t* stats,
                               const int32_t* entry_rows, void* stream);
+/*
+ * On-demand exact refine (ABI 15; DESIGN.md (d) "3-product bound, on-demand refine"): the bounded
+ * gather needs only 8 significant bits of every pair, and the refine reads the exact pair of a few
+ * dozen candidates per user, so the pair table need neither be fp32-faithful nor stay resident.
+ * The table stream writes hi words alone from the 3-product (fp16x3) kernels, the gather widens
+ * its intervals by a bound on the difference between that arithmetic and fp16x6, and the refine
+ * RECOMPUTES each surviving (history item, candidate) pair with the bits the fp16x6 table of the
+ * same job would hold. Same lists, ids and score bits as nais_pair_gather_topk on fp16x6 tables.
+ *   nais_pair_table_bound  the hi words of nais_pair_table_split at precision fp16x3 (same layout
+ *                      and bits), whatever params->precision says; no (e, e*s) pairs are stored.
+ *                      Native embed widths with hidden <= 128 (NAIS_E_UNSUPPORTED otherwise).
+ *   nais_pair_bound_topk_widened  nais_pair_bound_topk with widen = {eta, delta_s} (device floats;
+ *                      NULL or zeros: nais_pair_bound_topk exactly): every exact e lies within
+ *                      [1 - eta, 1 + eta] of the e whose truncation the hi word holds, and the two
+ *                      arithmetics' s = h . t differ by at most delta_s (absolute). The caller
+ *                      derives both from the weights (catalog.ondemand_widening).
+ *   nais_pair_scales   the power-of-two operand scales of the fp16x6 pair-table kernel for one job:
+ *                      row_scales[2r], [2r+1] = (S_A, S_h) of item row r (its 32-row chunk inside
+ *                      its 128-row group of the list), col_scales[c - col0] = S_t of column c (its
+ *                      32-column wave tile, counted from the first column of its table block; the
+ *                      blocks are block_cols wide from col0). Pure functions of the model and this
+ *                      geometry, which must be the one the tables would be built with.
+ *   nais_pair_refine_topk_exact  nais_pair_refine_topk without the ex tables: the pair values are
+ *                      recomputed from params and the scales. Other arguments as there.
+ *   nais_pair_recompute  out_e / out_es [num_rows][num_columns] = the recomputed (e, e*s) of table
+ *                      rows rows[] x POI columns columns[] (within [col0, col0 + cols)): the
+ *                      refine's arithmetic laid bare, bit-equal to nais_pair_table at fp16x6 for
+ *                      the same items, col0-block geometry and scales (tests/test_gpu_ondemand_refine.py).
+ * Shapes of the last three: NAIS_basic at precision fp16x6, embed_dim 32 or 64, hidden <= 64
+ * (NAIS_E_UNSUPPORTED otherwise; the caller keeps the split16 route).
+ */
+int32_t nais_pair_table_bound(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                              int64_t col0, int64_t cols, const int64_t* region_of,
+                              const double* coords, const double* latlon_mat, uint32_t* hi,
+                              int64_t ld, void* stream);
+int32_t nais_pair_bound_topk_widened(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
+                                     const int64_t* indptr, const int64_t* indices, const int32_t* users,
+                                     int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
+                                     uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv,
+                                     int32_t* surv_count, int32_t surv_cap, const int32_t* entry_rows,
+                                     const int64_t* spans, const float* widen, int32_t* work,
+                                     void* stream);
+int32_t nais_pair_scales(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                         int64_t col0, int64_t cols, int64_t block_cols, float* row_scales,
+                         float* col_scales, void* stream);
+int32_t nais_pair_refine_topk_exact(const nais_params_t* params, const float* row_scales,
+                                    const float* col_scales, const int32_t* rowmap, const int64_t* indptr,
+                                    const int64_t* indices, const int32_t* users, int32_t num_users,
+                                    int64_t col0, int64_t cols, int32_t k, const uint64_t* lo_keys,
+                                    const int32_t* lo_count, const uint64_t* surv, const int32_t* surv_count,
+                                    int32_t surv_cap, const uint64_t* tau, uint64_t* keys, int32_t* kcount,
+                                    int32_t* nan_count, int32_t* stats, const int32_t* entry_rows,
+                                    void* stream);
+int32_t nais_pair_recompute(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                            const float* row_scales, const float* col_scales, int64_t col0, int64_t cols,
+                            const int32_t* rows, int64_t num_rows, const int64_t* columns,
+                            int64_t num_columns, float* out_e, float* out_es, void* stream);
 /*
  * Power-law prior on the pairs route (powerLaw.py:86-92, run.py:537-539; the direct route's
  * nais_score_topk with a prior computes the same G rows per user):

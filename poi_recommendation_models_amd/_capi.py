@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -33,7 +33,9 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_pair_prior_table",
            "nais_pair_prior_gather", "nais_topk_blend_rows", "nais_topk_blend_rows_f64",
            "nais_topk_merge_f64", "nais_train_ucache_size", "nais_pair_table_split",
-           "nais_pair_bound_topk", "nais_pair_refine_topk")
+           "nais_pair_bound_topk", "nais_pair_refine_topk", "nais_pair_table_bound",
+           "nais_pair_bound_topk_widened", "nais_pair_scales", "nais_pair_refine_topk_exact",
+           "nais_pair_recompute")
 
 
 class NaisDotTables(ctypes.Structure):
@@ -233,6 +235,21 @@ def load(path: str | None = None):
     lib.nais_pair_refine_topk.restype = i32
     lib.nais_pair_refine_topk.argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, i32, i64, i64, f32, i32,
                                           vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.nais_pair_table_bound.restype = i32
+    lib.nais_pair_table_bound.argtypes = [ctypes.POINTER(NaisParams), vp, i64, i64, i64, vp, vp, vp, vp,
+                                          i64, vp]
+    lib.nais_pair_bound_topk_widened.restype = i32
+    lib.nais_pair_bound_topk_widened.argtypes = [vp, i64, vp, vp, vp, vp, i32, i64, i64, f32, i32, vp, vp,
+                                                 vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.nais_pair_scales.restype = i32
+    lib.nais_pair_scales.argtypes = [ctypes.POINTER(NaisParams), vp, i64, i64, i64, i64, vp, vp, vp]
+    lib.nais_pair_refine_topk_exact.restype = i32
+    lib.nais_pair_refine_topk_exact.argtypes = [ctypes.POINTER(NaisParams), vp, vp, vp, vp, vp, vp, i32,
+                                                i64, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                                vp, vp]
+    lib.nais_pair_recompute.restype = i32
+    lib.nais_pair_recompute.argtypes = [ctypes.POINTER(NaisParams), vp, i64, vp, vp, i64, i64, vp, i64,
+                                        vp, i64, vp, vp, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

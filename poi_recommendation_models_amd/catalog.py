@@ -273,10 +273,25 @@ PAIR_SPLIT_STEP = 8
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
 # candidates whose UPPER bound reaches the k-th of them, and a refine pass recomputes those
 # candidates' exact sums from their (e, e*s) pairs in CSR order: the same lists, ids and score bits as the exact
-# fused gather (tests/test_gpu_bounded.py compares every user). Every block's tables stay resident
-# until the refine (J x P x 8 bytes: 80 GB at config 4), so the route is taken only when they fit
-# the memory budget; otherwise the exact fused gather runs on double-buffered tables.
+# fused gather (tests/test_gpu_bounded.py compares every user). On the split16 form of the route
+# every block's tables stay resident until the refine (J x P x 12 bytes: 120 GB at config 4), so
+# it is taken only when they fit the memory budget; otherwise the exact fused gather runs on
+# double-buffered tables.
 PAIR_BOUNDED = True
+# 3-product bound + on-demand exact refine (include/nais.h, ABI 15): the gather
+# needs 8 significant bits of each pair and the refine the exact pair of a few dozen candidates
+# per user, so the table stream writes hi words alone from the 3-product (fp16x3) kernel into a
+# small ring of [J, ld] buffers (nais_pair_table_bound: half the matrix work of the fp16x6 table, a
+# third of its stores, nothing resident), the gather widens its intervals by a bound on the
+# difference between the two arithmetics (ondemand_widening: eta on the attention logit, delta_s
+# on h . t, from the weights alone) and the refine recomputes each (history item, survivor) pair
+# with the bits the fp16x6 table would hold (nais_pair_refine_topk_exact). Same lists, ids and
+# score bits. Taken when the bounded route is, the model is NAIS_basic at fp16x6 with embed_dim
+# (padded) 32 or 64 and hidden <= 64, and eta <= PAIR_ONDEMAND_ETA_MAX (2^-9 keeps the score
+# interval within ~1.5x of the split16 route's 2^-7; beyond it the survivor lists grow and the
+# premise is gone); "0" keeps the split16 route (A/B).
+PAIR_ONDEMAND_REFINE = os.environ.get("NAIS_PAIR_ONDEMAND_REFINE", "1") != "0"
+PAIR_ONDEMAND_ETA_MAX = 2.0 ** -9
 PAIR_SURV_CAP = 1024            # survivor keys per user (compacted by the current bound when full)
 # the bounded gather / refine get each CSR entry's table row and each slot's history span (ABI 14:
 # shorter chains of dependent loads); "0" passes NULL (A/B only). Per gather launch 2.272 -> 2.224
@@ -304,8 +319,71 @@ def bounded_gather_cu_seconds(entries, NC, users, k):
     return entries * NC * 4.0 / 90.4e9 + 512e-9 * users * launches + 68e-9 * users * ins
 
 
+def ondemand_widening(model):
+    """(widen, eta, delta_s) for nais_pair_bound_topk_widened on the 3-product bound route: widen =
+    device float32 [eta', delta_s]; eta' bounds |e3 / e6 - 1| and delta_s bounds |s3 - s6| over
+    EVERY (item, candidate) pair of the model, where (e6, s6) are the pair values of the fp16x6
+    table (what the refine ranks on) and (e3, s3) those of the 3-product table (what the hi words
+    truncate). Functions of the weights alone (DESIGN.md (d) has the derivation): with u = 2^-23,
+    D the padded width, HP the padded hidden size,
+      H2, T2 = the largest row 2-norms of embed_history / embed_target, Hinf, Tinf their largest
+      elements, Winf_i = max_k |W1[i, k]|, Z_i = |b1_i| + Winf_i H2 T2 (Cauchy-Schwarz over k),
+      g(n) = n u / (1 - n u)   any-order fp32 accumulation of n terms, each addition within u,
+      q = D 2^-36 max_i Winf_i Hinf Tinf   the f16 subnormal quanta of both splits,
+      theta = (g(6 D + 1) + g(3 D + 1)) (1 + 2^-8) + 2^-23 + 2^-20   both accumulations, both splits,
+      eta_a = sum_i |w2_i| (theta Z_i + q + (HP + 4) u 1.01 Z_i)     the w2 . ReLU step is 1-Lipschitz,
+      eta'  = eta_a (1 + eta_a) + 2^-20   (two expf calls),  delta_s = theta H2 T2 + q / max Winf.
+    Cached on the parameters' (data_ptr, version counter), as model._score_params caches its padded
+    copies: recomputed (one host sync) only after they change. Here a stale hit is a soundness
+    matter, not a stale copy -- bounds that no longer cover the pairs can drop a true winner
+    silently -- so the contract is: whoever writes the parameters bumps their version counters.
+    Every in-place torch op, load_state_dict, the optimizers and the in-tree trainer do; a write
+    through `.data`, or by a kernel given the raw pointer, does not, and must be followed by
+    `model.__dict__.pop("_widen_cache", None)` (or any in-place op on the tensor)."""
+    eh, et = model._item_tables()
+    w1, b1, w2 = model.attn_layer1.weight, model.attn_layer1.bias, model.attn_layer2.weight
+    srcs = (eh, et, w1, b1, w2)
+    key = tuple((t.data_ptr(), t._version) for t in srcs)
+    hit = model.__dict__.get("_widen_cache")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    with torch.no_grad():
+        f64 = torch.float64
+        D = next((w for w in (8, 16, 32, 64, 128) if w >= w1.shape[1]), w1.shape[1])
+        HP = 32 if w1.shape[0] <= 32 else 64
+        u = 2.0 ** -23
+        g = lambda n: n * u / (1.0 - n * u)
+        H2 = torch.linalg.vector_norm(eh.to(f64), dim=1).max()
+        T2 = torch.linalg.vector_norm(et.to(f64), dim=1).max()
+        Hinf, Tinf = eh.abs().max().to(f64), et.abs().max().to(f64)
+        Winf = w1.abs().amax(dim=1).to(f64)
+        Z = b1.abs().to(f64) + Winf * H2 * T2
+        q = D * 2.0 ** -36 * Winf.max() * Hinf * Tinf
+        theta = (g(6 * D + 1) + g(3 * D + 1)) * (1 + 2.0 ** -8) + 2.0 ** -23 + 2.0 ** -20
+        eta_a = (w2.abs().to(f64).reshape(-1) * (theta * Z + q + (HP + 4) * u * 1.01 * Z)).sum()
+        eta = eta_a * (1 + eta_a) + 2.0 ** -20
+        ds = theta * H2 * T2 + D * 2.0 ** -36 * Hinf * Tinf
+        # the scales are clamped at 2^+-120: operands far outside fp32's middle range void the
+        # quanta argument (and a non-finite weight everything): no bound then
+        ok = ((Winf.max() * Hinf < 2.0 ** 100) & (Winf.max() * Hinf > 2.0 ** -100) &
+              (Tinf < 2.0 ** 100) & (Tinf > 2.0 ** -100))
+        both = torch.stack([eta, ds]) * (1 + 2.0 ** -20)   # rounded to float32 below, upwards
+        both = torch.where(ok & torch.isfinite(both).all(), both, torch.full_like(both, float("inf")))
+        widen = both.to(torch.float32)
+        eta_h, ds_h = (float(v) for v in both.cpu())
+    out = (widen, eta_h, ds_h)
+    model.__dict__["_widen_cache"] = (key, out)
+    return out
+
+
+def _ondemand_shape(model, prm):
+    """The shapes nais_pair_refine_topk_exact covers (include/nais.h)."""
+    return (prm.variant == _capi.VARIANT_BASIC and prm.precision == _capi.PRECISION_FP16X6
+            and prm.embed_dim in (32, 64) and prm.hidden <= 64)
+
+
 def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, work_queues=True,
-                   gather_bytes=8, k=None, users=None):
+                   gather_bytes=8, k=None, users=None, products=None):
     """CUs for the table stream (the rest gather), in steps of ncu / 8 (counts off a multiple of 32
     leave a shader engine short and lose -- DESIGN.md, CU split), from a cost model fitted
     on config 4 and config 5 (profiles/r1/cfg5p/, re-fitted in round 3 on the fp16x6 tables:
@@ -317,13 +395,18 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     pr_d table (~1.4e-11 s per pair on the whole chip, profiles/r2/legs_s4) and the gather stream
     reads it too (8 more bytes per history entry and column).
 
+    `products`: the table kernel's f16 products per fp32 product when it is not the model's own
+    precision (the 3-product bound table of PAIR_ONDEMAND_REFINE; x3b has no work queue, so the
+    split then moves in shader-engine steps).
+
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
     split step finer than one CU per shader engine: a fixed-grid launch on a CU count off a
     multiple of 32 leaves an engine short and runs at the next lower multiple."""
     H, din = model.attn_layer1.weight.shape
     prec = getattr(model, "precision", "fp16x6")
-    products = 1 if prec == "fp32" else (6 if prec.startswith("fp16x6") else 3)
+    if products is None:   # given: the 3-product bound table under an fp16x6 model
+        products = 1 if prec == "fp32" else (6 if prec.startswith("fp16x6") else 3)
     dist = getattr(model, "VARIANT", 0) in (_capi.VARIANT_REGION_DISTANCE, _capi.VARIANT_DISTANCE)
     D = din - 2 if dist else din
     D = next((w for w in (8, 16, 32, 64, 128) if w >= D), D)   # the padded width the kernels run
@@ -518,6 +601,16 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
              and type(model)._pair_fixup is _NAISDevice._pair_fixup)
     # the bounded route needs the split16 tables of the NAIS modules' own table kernels
     bounded_ok = fused and PAIR_BOUNDED and type(model)._pair_table is _NAISDevice._pair_table
+    # the 3-product bound + on-demand refine form of it: decided from the model and the shape alone
+    # (every rank of a tau_group decides alike); eta beyond the threshold keeps the split16 form
+    ond = None
+    if bounded_ok and PAIR_ONDEMAND_REFINE and _ondemand_shape(model, prm):
+        widen, eta, ds = ondemand_widening(model)
+        if np.isfinite(eta) and eta <= PAIR_ONDEMAND_ETA_MAX:
+            ond = widen
+        if events is not None:
+            events.extend((("ondemand_eta", None, None, eta), ("ondemand_delta_s", None, None, ds),
+                           ("ondemand_eta_accepted", None, None, ond is not None)))
     if prior is not None:
         pa, pb, alpha, pc = prior
         pri_coords = torch.as_tensor(np.ascontiguousarray(pc, dtype=np.float64)).to(dev)
@@ -542,6 +635,11 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
         return wq_of[h]
 
     def table(tab, c0, w, stream_):
+        if isinstance(tab, tuple) and len(tab) == 1:   # on-demand refine: hi words alone, 3 products
+            _capi.check(lib.nais_pair_table_bound(prm, items.data_ptr(), J, c0, w, _capi.ptr(reg),
+                                                  _capi.ptr(cor), _capi.ptr(llm), tab[0].data_ptr(),
+                                                  ld, stream_), "nais_pair_table_bound")
+            return
         if isinstance(tab, tuple):   # the bounded route's split16 tables (hi words, ex pairs)
             _capi.check(lib.nais_pair_table_split(prm, items.data_ptr(), J, c0, w, _capi.ptr(reg),
                                                   _capi.ptr(cor), _capi.ptr(llm), tab[0].data_ptr(),
@@ -576,6 +674,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
         if b0 > 0 or m < n:
             J = rows(u_dev, m)
         bnd = [False]   # this pass takes the bounded route (decided once the tables are sized)
+        ondm = [False]  # ... in its 3-product bound + on-demand refine form
 
         def gather_launches(w):   # one fused-gather kernel per 256-column (bounded: 512) stripe
             stripe = PAIR_BOUNDED_STRIPE if bnd[0] else PAIR_STRIPE
@@ -589,14 +688,14 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 if b <= a:
                     return
                 if bnd[0]:
-                    _capi.check(lib.nais_pair_bound_topk(
+                    _capi.check(lib.nais_pair_bound_topk_widened(
                         tab[0].data_ptr(), ld, rowmap.data_ptr(), csr.indptr.data_ptr(), csr.indices.data_ptr(),
                         u_dev.data_ptr() + 4 * a, b - a, c0, w, float(model.beta), k,
                         lokeys.data_ptr() + 8 * k * a, locount.data_ptr() + 4 * a,
                         surv.data_ptr() + 8 * PAIR_SURV_CAP * a, scount.data_ptr() + 4 * a, PAIR_SURV_CAP,
                         _capi.ptr(erows), spans.data_ptr() + 16 * a if spans is not None else None,
-                        wq(stream_), stream_),
-                        "nais_pair_bound_topk")
+                        ond.data_ptr() if ondm[0] else None, wq(stream_), stream_),
+                        "nais_pair_bound_topk_widened")
                     return
                 _capi.check(lib.nais_pair_gather_topk(
                     tab[0].data_ptr(), tab[1].data_ptr(), ld, rowmap.data_ptr(), csr.indptr.data_ptr(),
@@ -631,12 +730,32 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
             # the per-user lower-bound lists and survivor keys
             bnd[0] = bounded_ok and (len(blocks) * 3 * J * ld * 4 + m * (PAIR_SURV_CAP + k) * 8
                                      <= budget)
+            lists = m * (PAIR_SURV_CAP + 2 * k) * 8   # lokeys, surv and the keys
+            # on-demand refine: what it actually allocates -- the ring of hi buffers (one per table
+            # stream plus one), the lists, the per-entry rows and per-slot spans, the scale arrays
+            nring = max(1, PAIR_TABLE_STREAMS) + 1
+            ondm[0] = (ond is not None and nring * J * ld * 4 + lists + entries * 4 + m * 24
+                       + (2 * J + NC) * 4 <= budget)
             if tau_group is not None and bounded_ok:   # the same route on every rank
                 from .sharding import agree_min
                 bnd[0] = bool(agree_min(int(bnd[0]), dev, tau_group))
-            if bnd[0]:   # per block: the hi words [J, ld] and the exact (e, e*s) pairs [J, 2 ld]
-                arena = (torch.empty(len(blocks), J, ld, dtype=torch.int32, device=dev),
-                         torch.empty(len(blocks), J, 2 * ld, dtype=torch.int32, device=dev))
+                if ond is not None:
+                    ondm[0] = bool(agree_min(int(ondm[0]), dev, tau_group))
+            bnd[0] = bnd[0] or ondm[0]
+            if events is not None:
+                events.append(("pair_route", None, None, "ondemand" if ondm[0] else
+                               ("split16" if bnd[0] else "exact")))
+            if bnd[0]:
+                if ondm[0]:   # a ring of hi-word buffers [J, ld], reused behind their gathers
+                    ring = [torch.empty(J, ld, dtype=torch.int32, device=dev) for _ in range(nring)]
+                    ring_done = [None] * nring
+                    rowsc = torch.empty(max(J, 1), 2, dtype=torch.float32, device=dev)
+                    colsc = torch.empty(NC, dtype=torch.float32, device=dev)
+                    arena = ()
+                else:   # per block: the hi words [J, ld] and the exact (e, e*s) pairs [J, 2 ld]
+                    arena = (torch.empty(len(blocks), J, ld, dtype=torch.int32, device=dev),
+                             torch.empty(len(blocks), J, 2 * ld, dtype=torch.int32, device=dev))
+                    ring = []
                 lokeys = torch.empty(m, k, dtype=torch.int64, device=dev)
                 locount = torch.zeros(m, dtype=torch.int32, device=dev)
                 surv = torch.empty(m, PAIR_SURV_CAP, dtype=torch.int64, device=dev)
@@ -655,9 +774,10 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
             # both streams run as work queues only with the NAIS modules' own table kernel and
             # the fused gather (the score-row gather and nais_dot_pair_table keep fixed grids)
             wq_both = fused and type(model)._pair_table is _NAISDevice._pair_table
-            table_cus = (auto_table_cus(model, J, NC, entries, ncu, prior is not None, J * ld * 8,
+            table_cus = (auto_table_cus(model, J, NC, entries, ncu, prior is not None,
+                                        J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
-                                        users=m)
+                                        users=m, products=3 if ondm[0] else None)
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
             wq_on[0] = table_cus % max(1, ncu // 8) != 0
             if events is not None:
@@ -675,7 +795,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 first_all = PAIR_FIRST_TABLE_ALL_CUS
                 if first_all:      # block 0's table alone, on the caller's stream (all CUs)
                     w0 = min(W, c1_all - blocks[0])
-                    tab0 = (arena[0][0], arena[1][0]) if bnd[0] else tabs[0]
+                    tab0 = ((ring[0],) if ondm[0] else (arena[0][0], arena[1][0])) if bnd[0] else tabs[0]
                     timed("table", lambda: table(tab0, blocks[0], w0, st))
                 for t_ in tss:
                     t_.wait_stream(torch_stream)
@@ -694,11 +814,14 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                     events.append(("gather_share", None, None, share))
             for b, c0 in enumerate(blocks):
                 w = min(W, c1_all - c0)
-                tab = (arena[0][b], arena[1][b]) if bnd[0] else tabs[b % len(tabs)]
+                tab = (((ring[b % len(ring)],) if ondm[0] else (arena[0][b], arena[1][b])) if bnd[0]
+                       else tabs[b % len(tabs)])
                 if overlap:
                     tsb = tss[b % len(tss)]
                     if done_g[b % 2] is not None and not bnd[0]:
                         tsb.wait_event(done_g[b % 2])    # buffer free: its gather finished
+                    if ondm[0] and ring_done[b % len(ring)] is not None:
+                        tsb.wait_event(ring_done[b % len(ring)])   # ring buffer free likewise
                     if not (b == 0 and first_all):
                         e_t0, e_t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         e_t0.record(tsb)
@@ -712,6 +835,8 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                     gather(tab, c0, w, gs.cuda_stream, 0, m1)
                     e_g1.record(gs)
                     done_g[b % 2] = e_g1
+                    if ondm[0]:
+                        ring_done[b % len(ring)] = e_g1
                     if events is not None:
                         events.append(("gather", e_g0, e_g1, gather_launches(w)))
                     if m1 < m:   # the tail users, behind this block's table on the table stream
@@ -730,7 +855,9 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 for t_ in tss:
                     torch_stream.wait_stream(t_)
                 for t in [*tabs, *pr_of.values(), *([wq_slots] if wq_slots is not None else []),
-                          *((*arena, lokeys, locount, surv, scount,
+                          # (the widening array is not among them: it lives on the model, allocated
+                          # on the caller's stream, which waits for the side streams above)
+                          *((*arena, *ring, lokeys, locount, surv, scount,
                              *((erows, spans) if erows is not None else ())) if bnd[0] else ())]:
                     for t_ in (*tss, gs):   # not handed to the main stream early
                         t.record_stream(t_)
@@ -740,15 +867,30 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 if tau_group is not None:   # the k-th lower key over every rank's columns
                     from .sharding import global_kth_keys
                     tau_g = timed("tau_exchange", lambda: global_kth_keys(lokeys, locount, k, tau_group))
-                timed("refine", lambda: _capi.check(lib.nais_pair_refine_topk(
-                    arena[1].data_ptr(), 2 * J * ld, ld, W, rowmap.data_ptr(), csr.indptr.data_ptr(),
-                    csr.indices.data_ptr(), u_dev.data_ptr(), m, c0_all, NC, float(model.beta), k,
-                    lokeys.data_ptr(), locount.data_ptr(), surv.data_ptr(), scount.data_ptr(),
-                    PAIR_SURV_CAP, tau_g.data_ptr() if tau_g is not None else None, keys.data_ptr(),
-                    kcount.data_ptr(), counters[0:1].data_ptr(), stats.data_ptr(), _capi.ptr(erows), st),
-                    "nais_pair_refine_topk"))
+                if ondm[0]:
+                    # the fp16x6 table kernel's operand scales for this job's geometry (blocks of W
+                    # columns from c0_all), then the refine that recomputes the survivors' pairs
+                    timed("scales", lambda: _capi.check(lib.nais_pair_scales(
+                        prm, items.data_ptr(), J, c0_all, NC, W, rowsc.data_ptr(), colsc.data_ptr(), st),
+                        "nais_pair_scales"))
+                    timed("refine", lambda: _capi.check(lib.nais_pair_refine_topk_exact(
+                        prm, rowsc.data_ptr(), colsc.data_ptr(), rowmap.data_ptr(), csr.indptr.data_ptr(),
+                        csr.indices.data_ptr(), u_dev.data_ptr(), m, c0_all, NC, k,
+                        lokeys.data_ptr(), locount.data_ptr(), surv.data_ptr(), scount.data_ptr(),
+                        PAIR_SURV_CAP, tau_g.data_ptr() if tau_g is not None else None, keys.data_ptr(),
+                        kcount.data_ptr(), counters[0:1].data_ptr(), stats.data_ptr(), _capi.ptr(erows),
+                        st), "nais_pair_refine_topk_exact"))
+                    del rowsc, colsc
+                else:
+                    timed("refine", lambda: _capi.check(lib.nais_pair_refine_topk(
+                        arena[1].data_ptr(), 2 * J * ld, ld, W, rowmap.data_ptr(), csr.indptr.data_ptr(),
+                        csr.indices.data_ptr(), u_dev.data_ptr(), m, c0_all, NC, float(model.beta), k,
+                        lokeys.data_ptr(), locount.data_ptr(), surv.data_ptr(), scount.data_ptr(),
+                        PAIR_SURV_CAP, tau_g.data_ptr() if tau_g is not None else None, keys.data_ptr(),
+                        kcount.data_ptr(), counters[0:1].data_ptr(), stats.data_ptr(), _capi.ptr(erows), st),
+                        "nais_pair_refine_topk"))
                 model._last_bound_stats = stats
-                del arena, lokeys, locount, surv, scount, erows, spans
+                del arena, ring, lokeys, locount, surv, scount, erows, spans
             del tabs
             pr_of.clear()
             if not fused:

@@ -32,6 +32,7 @@
 #include "nais.h"
 #include "nais_internal.h"
 #include "nais_geo.h"
+#include "nais_fp16x6.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -86,7 +87,7 @@ __device__ __forceinline__ void tab_put(const TableOut& t, int64_t row, int64_t 
   t.e[o] = __uint_as_float(__builtin_amdgcn_perm(sb, eb, t.sel_e));
   if (t.ex) {
     reinterpret_cast<float2*>(t.es)[o] = make_float2(e, es);
-  } else {
+  } else if (t.es) {   // null: the hi words alone (nais_pair_table_bound)
     t.es[o] = es;
   }
 }
@@ -520,90 +521,9 @@ forward_kernel(DevParams p, const int64_t* __restrict__ hist, int64_t b, int64_t
 //         applied to t_c (so x_s = t_s * h_j = S_t * fl32(t_c * h_j) exactly).
 // b1 / w2 are pre-scaled per chunk so acc = S_w*S_t*(W1 x + b1) and a_j = sum w2/(S_w S_t) relu(acc).
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ floatx16 mfma16(half8 a, half8 b, floatx16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-// 2^e with m * 2^e in [2^13, 2^14) for finite m > 0 (clamped), 1 otherwise
-__device__ __forceinline__ float pow2_scale(float m) {
-  if (!(m > 0.f) || !(m < __builtin_huge_valf())) return 1.f;
-  const uint32_t bits = __float_as_uint(m);
-  int ex = (int)((bits >> 23) & 255u) - 127;
-  if (((bits >> 23) & 255u) == 0u) ex = -127;  // subnormal product: maximal (clamped) scale
-  int e = 13 - ex;
-  e = e < -120 ? -120 : (e > 120 ? 120 : e);
-  return __uint_as_float((uint32_t)(e + 127) << 23);
-}
-
-// x -> (hi, lo): hi = f16(x) (RNE, v_cvt_pk_f16_f32), lo = f16(x - hi) with the subtraction done
-// exactly inside v_fma_mix{lo,hi}_f16 (one instruction per element instead of cvt + sub + cvt).
-// The trailing s_nop 1 covers the VALU-write -> MFMA-operand-read hazard that hipcc does not
-// pad for inline asm (cdna_hip_programming.md 5.7 item 2).
-__device__ __forceinline__ void split8(const float (&x)[8], half8& hi, half8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) hi[e] = (_Float16)x[e];
-  const uint4 hu = *reinterpret_cast<const uint4*>(&hi);
-  uint32_t l0, l1, l2, l3;
-  asm("v_fma_mixlo_f16 %0, -%4, 1.0, %8 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, -%4, 1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %1, -%5, 1.0, %10 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %1, -%5, 1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %2, -%6, 1.0, %12 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %2, -%6, 1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %3, -%7, 1.0, %14 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %3, -%7, 1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "s_nop 1"
-      : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-      : "v"(hu.x), "v"(hu.y), "v"(hu.z), "v"(hu.w), "v"(x[0]), "v"(x[1]), "v"(x[2]), "v"(x[3]),
-        "v"(x[4]), "v"(x[5]), "v"(x[6]), "v"(x[7]));
-  const uint4 lu = make_uint4(l0, l1, l2, l3);
-  lo = *reinterpret_cast<const half8*>(&lu);
-}
-
-// x -> (hi, mid, lo), x == hi + mid + lo exactly for the scaled operands of this file (33
-// significant bits >= fp32's 24; f16 subnormals only below 2^-37 of the scaled maximum):
-//   hi = f16(x),  r = x - hi (exact, v_fma_mix_f32),  mid = f16(r),  lo = f16(r - mid) (exact
-//   subtraction inside v_fma_mix{lo,hi}_f16). The fp16x6 path multiplies such splits (6 products).
-__device__ __forceinline__ void split8_3(const float (&x)[8], half8& hi, half8& mid, half8& lo) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) hi[e] = (_Float16)x[e];
-  const uint4 hu = *reinterpret_cast<const uint4*>(&hi);
-  const uint32_t hw[4] = {hu.x, hu.y, hu.z, hu.w};
-  float r[8];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    asm("v_fma_mix_f32 %0, -%2, 1.0, %3 op_sel_hi:[1,0,0]\n\t"
-        "v_fma_mix_f32 %1, -%2, 1.0, %4 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-        : "=&v"(r[2 * q]), "=&v"(r[2 * q + 1])
-        : "v"(hw[q]), "v"(x[2 * q]), "v"(x[2 * q + 1]));
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) mid[e] = (_Float16)r[e];
-  const uint4 mu = *reinterpret_cast<const uint4*>(&mid);
-  uint32_t l0, l1, l2, l3;
-  asm("v_fma_mixlo_f16 %0, -%4, 1.0, %8 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %0, -%4, 1.0, %9 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %1, -%5, 1.0, %10 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %1, -%5, 1.0, %11 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %2, -%6, 1.0, %12 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %2, -%6, 1.0, %13 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixlo_f16 %3, -%7, 1.0, %14 op_sel_hi:[1,0,0]\n\t"
-      "v_fma_mixhi_f16 %3, -%7, 1.0, %15 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
-      "s_nop 1"
-      : "=&v"(l0), "=&v"(l1), "=&v"(l2), "=&v"(l3)
-      : "v"(mu.x), "v"(mu.y), "v"(mu.z), "v"(mu.w), "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]),
-        "v"(r[4]), "v"(r[5]), "v"(r[6]), "v"(r[7]));
-  const uint4 lu = make_uint4(l0, l1, l2, l3);
-  lo = *reinterpret_cast<const half8*>(&lu);
-}
-
-// NPC split pieces of 8 fp32 values: 2 = (hi, lo) for fp16x3, 3 = (hi, mid, lo) for fp16x6
-template <int NPC>
-__device__ __forceinline__ void split_pieces(const float (&x)[8], half8 (&pc)[NPC]) {
-  if constexpr (NPC == 2) split8(x, pc[0], pc[1]);
-  else split8_3(x, pc[0], pc[1], pc[2]);
 }
 
 // c += a . b over the pieces, smallest terms first:
@@ -670,13 +590,6 @@ struct Consts16 {
   static constexpr int EPI = 2 * 2 * HB * 16;
   static constexpr size_t BYTES = size_t(A16) * 16 + size_t(ADIST) * 4 + size_t(EPI) * 4 + 64;
 };
-
-// ReLU that keeps every NaN, as torch.relu (model.py:71): gfx950's v_maximum3_f32 (IEEE 754-2019
-// maximum: NaN propagates, max(-0, +0) = +0), one VALU. (The round-2 form, v_cmp + v_cndmask on
-// the float bits, was 1.1 % slower on the pair table: profiles/r3/relu_ab.)
-__device__ __forceinline__ float relu_bits(float v) {
-  return __builtin_elementwise_maximum(v, 0.f);   // v_maximum3_f32: IEEE maximum, NaN in -> NaN out
-}
 
 template <int HB, bool REGS>
 struct Epi16;
@@ -1440,22 +1353,6 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
 // feature of one pair -- lane group g: feature g >> 1 of candidate block g & 1 -- and one
 // v_permlane32_swap hands every lane both features of its block.
 // ---------------------------------------------------------------------------------------------
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ floatx4 mfma16n(half8 a, half8 b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-// the six fp16x6 products, smallest terms first (as mfma_pieces<3>)
-__device__ __forceinline__ floatx4 mfma16n_pieces(const half8 (&a)[3], const half8 (&b)[3], floatx4 c) {
-  c = mfma16n(a[2], b[0], c);
-  c = mfma16n(a[1], b[1], c);
-  c = mfma16n(a[0], b[2], c);
-  c = mfma16n(a[1], b[0], c);
-  c = mfma16n(a[0], b[1], c);
-  c = mfma16n(a[0], b[0], c);
-  return c;
-}
-
 // A "unit" is one item's A_j restricted to MB blocks of 16 hidden units; NHU units make the item,
 // whose logit partials are summed before the tail. The ring holds 2 groups of GU units: GU = 2
 // where a unit is <= 24 KiB, else 1 (a whole D = H = 128 item, 96 KiB, does not fit twice in the
@@ -2089,6 +1986,64 @@ catalog_score_x6n_kernel(DevParams p, const int64_t* __restrict__ indptr,
     }
   }
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The power-of-two scales catalog_score_x6n_kernel uses in pair-table mode, as arrays, for the
+// on-demand exact refine (nais_pairs.hip pair_exact_*), which recomputes single pairs of that
+// table bit for bit and so needs the scale every operand was split under. They are pure functions
+// of the model and the job's geometry (NAIS_basic, one hidden slice, D <= 64):
+//   rowsc[2 r]     = S_A = pow2_scale(Wmax * Hm)   Hm = max |h| over row r's chunk: CfgN::JCB rows
+//   rowsc[2 r + 1] = S_h = pow2_scale(Hm)               inside its PAIR_GROUP_ITEMS group of the list
+//   colsc[c - col0] = S_t = pow2_scale(tmax)       tmax over the 32 candidate rows of c's wave tile,
+//       tiles counted from the first column of c's table block (blocks of bcols columns from
+//       col0), lanes past the block's end clamped to row P - 1 as the kernel clamps them.
+// One wave per row chunk (blocks [0, nchunks)) or column tile (the rest).
+template <int D>
+__global__ void __launch_bounds__(64)
+pair_scales_kernel(DevParams p, const int64_t* __restrict__ items, int64_t nitems, int64_t col0,
+                   int64_t cols, int64_t bcols, int64_t nchunks, float* __restrict__ rowsc,
+                   float* __restrict__ colsc) {
+  constexpr int JCB = CfgN<D, 2, 1>::JCB;
+  static_assert(JCB == CfgN<D, 4, 1>::JCB && PAIR_GROUP_ITEMS % JCB == 0 && JCB == 32, "x6n chunk rows");
+  const int lane = threadIdx.x, r32 = lane & 31, half = lane >> 5;
+  auto row_max = [&](const float* row) {   // this lane's half of a D-float row
+    float m = 0.f;
+#pragma unroll
+    for (int q = 0; q < D / 8; ++q) {
+      const float4 v = reinterpret_cast<const float4*>(row + half * (D / 2))[q];
+      m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    }
+    return m;
+  };
+  auto wave_max = [&](float m) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    return m;
+  };
+  const int64_t b = blockIdx.x;
+  if (b < nchunks) {
+    const int64_t r0 = b * JCB;   // groups are multiples of the chunk, so chunks tile the list
+    const int64_t gend = std::min<int64_t>(nitems, (r0 / PAIR_GROUP_ITEMS + 1) * PAIR_GROUP_ITEMS);
+    const int jn = (int)std::min<int64_t>(JCB, gend - r0);
+    float wmax = 0.f;
+    for (int f = lane; f < p.H * D; f += 64) wmax = fmaxf(wmax, fabsf(p.w1[(int64_t)(f / D) * p.din + f % D]));
+    const float Wmax = wave_max(wmax);
+    const float Hm = wave_max(r32 < jn ? row_max(p.eh + items[r0 + r32] * p.item_dim) : 0.f);
+    if (lane < jn) {
+      rowsc[2 * (r0 + lane)] = pow2_scale(Wmax * Hm);
+      rowsc[2 * (r0 + lane) + 1] = pow2_scale(Hm);
+    }
+    return;
+  }
+  const int64_t tpb = (bcols + 31) / 32;          // wave tiles per table block
+  const int64_t t = b - nchunks, blk = t / tpb;
+  const int64_t c0 = col0 + blk * bcols;
+  const int64_t clim = std::min<int64_t>(p.P, std::min<int64_t>(c0 + bcols, col0 + cols));
+  const int64_t c = c0 + (t % tpb) * 32 + r32;
+  if (c - r32 >= clim) return;                    // the block's last tile ends before this one
+  const float St = pow2_scale(wave_max(row_max(p.et + (c < clim ? c : p.P - 1) * p.item_dim)));
+  if (half == 0 && c < clim) colsc[c - col0] = St;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3099,14 +3054,16 @@ namespace {
 int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64_t num_items,
                         int64_t col0, int64_t cols, const int64_t* region_of, const double* coords,
                         const double* latlon_mat, float* e, float* es, int64_t ld, int32_t* work,
-                        void* stream, bool split = false) {
+                        void* stream, bool split = false, bool bound = false) {
+  // bound: the hi words of the split16 form alone, from the 3-product (fp16x3) kernels whatever
+  // params->precision says -- es stays null and no (e, e*s) pair is stored (nais_pair_table_bound)
   Shape sh;
   int rc = validate(params, &sh);
   if (rc) return rc;
   if (num_items < 0 || col0 < 0 || cols < 0 || col0 + cols > params->num_pois)
     return fail(NAIS_E_INVALID, "bad item count or column range");
   if (num_items == 0 || cols == 0) return NAIS_OK;
-  if (!items || !e || !es) return fail(NAIS_E_INVALID, "missing pointer");
+  if (!items || !e || (!es && !bound)) return fail(NAIS_E_INVALID, "missing pointer");
   if (ld < cols) return fail(NAIS_E_INVALID, "ld < cols");
   if ((params->variant == NAIS_VARIANT_REGION || params->variant == NAIS_VARIANT_REGION_DISTANCE) &&
       !region_of)
@@ -3118,14 +3075,15 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
   DevParams d;
   rc = to_dev(params, &d);
   if (rc) return rc;
+  if (bound && (sh.gen_tab || sh.HB > 4))
+    return fail(NAIS_E_UNSUPPORTED, "nais_pair_table_bound: native embed widths with hidden <= 128 only");
   if (sh.gen_tab)
     return nais_gx_catalog(params, nullptr, nullptr, nullptr, 0, items, num_items, col0, cols,
                            region_of, coords, latlon_mat, nullptr, 0, nullptr, e, es, ld, st, split);
+  const int precision = bound ? NAIS_PRECISION_FP16X3 : params->precision;
   TableOut tab;
-  if (split) {
-    tab.sel_e = NAIS_SEL_HI;
-    tab.ex = 1;
-  }
+  if (split || bound) tab.sel_e = NAIS_SEL_HI;
+  if (split) tab.ex = 1;
   tab.ld = ld;
   tab.cols = cols;
   tab.gi = PAIR_GROUP_ITEMS;
@@ -3135,14 +3093,13 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
     const int64_t base = g0 * tab.gi;
     tab.nitems = std::min<int64_t>(num_items - base, groups_per_launch * tab.gi);
     tab.e = e + base * ld;
-    tab.es = es + base * ld * (split ? 2 : 1);
+    tab.es = es ? es + base * ld * (split ? 2 : 1) : nullptr;
     tab.col0 = col0;
     const int ng = (int)((tab.nitems + tab.gi - 1) / tab.gi);
-    if (params->precision == NAIS_PRECISION_FP32)
+    if (precision == NAIS_PRECISION_FP32)
       NAIS_DISPATCH(launch_catalog, sh.DH, sh.HB, params->variant, d, nullptr, items + base, nullptr,
                     ng, region_of, coords, latlon_mat, nullptr, 0, nullptr, st, tab);
-    else if (params->precision == NAIS_PRECISION_FP16X6 ||
-             params->precision == NAIS_PRECISION_FP16X6_PAIRSPLIT)
+    else if (precision == NAIS_PRECISION_FP16X6 || precision == NAIS_PRECISION_FP16X6_PAIRSPLIT)
       NAIS_DISPATCH(launch_catalog_x6b, sh.DH, sh.HB, params->variant, d, nullptr, items + base,
                     nullptr, ng, region_of, coords, latlon_mat, nullptr, 0, nullptr, st, tab);
     else
@@ -3169,6 +3126,46 @@ int32_t nais_pair_table_split(const nais_params_t* params, const int64_t* items,
   return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
                          reinterpret_cast<float*>(hi), reinterpret_cast<float*>(ex), ld, work, stream,
                          true);
+}
+
+int32_t nais_pair_table_bound(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                              int64_t col0, int64_t cols, const int64_t* region_of,
+                              const double* coords, const double* latlon_mat, uint32_t* hi,
+                              int64_t ld, void* stream) {
+  return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
+                         reinterpret_cast<float*>(hi), nullptr, ld, nullptr, stream, false, true);
+}
+
+int32_t nais_pair_scales(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                         int64_t col0, int64_t cols, int64_t block_cols, float* row_scales,
+                         float* col_scales, void* stream) {
+  Shape sh;
+  int rc = validate(params, &sh);
+  if (rc) return rc;
+  // the shapes nais_pair_refine_topk_exact covers: the x6n kernel with one hidden slice, no
+  // region / distance operands
+  if (params->variant != NAIS_VARIANT_BASIC || params->precision != NAIS_PRECISION_FP16X6 ||
+      (params->embed_dim != 32 && params->embed_dim != 64) || params->hidden > 64)
+    return fail(NAIS_E_UNSUPPORTED, "nais_pair_scales: NAIS_basic at fp16x6, embed_dim 32 or 64, hidden <= 64");
+  if (num_items < 0 || col0 < 0 || cols < 0 || col0 + cols > params->num_pois || block_cols <= 0)
+    return fail(NAIS_E_INVALID, "bad item count, column range or block width");
+  if (num_items == 0 && cols == 0) return NAIS_OK;
+  if ((num_items > 0 && (!items || !row_scales)) || (cols > 0 && !col_scales))
+    return fail(NAIS_E_INVALID, "missing pointer");
+  DevParams d;
+  rc = to_dev(params, &d);
+  if (rc) return rc;
+  const int64_t nchunks = (num_items + 31) / 32;
+  const int64_t ntiles = (cols + block_cols - 1) / block_cols * ((block_cols + 31) / 32);
+  if (nchunks + ntiles > 0x7FFFFFFFll) return fail(NAIS_E_UNSUPPORTED, "too many rows or columns");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (params->embed_dim == 32)
+    hipLaunchKernelGGL(pair_scales_kernel<32>, dim3((unsigned)(nchunks + ntiles)), dim3(64), 0, st, d, items,
+                       num_items, col0, cols, block_cols, nchunks, row_scales, col_scales);
+  else
+    hipLaunchKernelGGL(pair_scales_kernel<64>, dim3((unsigned)(nchunks + ntiles)), dim3(64), 0, st, d, items,
+                       num_items, col0, cols, block_cols, nchunks, row_scales, col_scales);
+  return check_launch("pair_scales_kernel");
 }
 
 int32_t nais_score_catalog(const nais_params_t* params, const int64_t* indptr,

@@ -24,6 +24,7 @@
 #include "nais.h"
 #include "nais_internal.h"
 #include "nais_geo.h"
+#include "nais_fp16x6.h"
 
 namespace {
 
@@ -611,13 +612,34 @@ struct Bounds {
   float slo, shi, nlo, nhi, dlo, dhi;
   bool ok;
 };
-__device__ __forceinline__ Bounds make_bounds(float S, float N, float A, int64_t hl, float beta) {
+// Widening for hi words that truncate the terms of ANOTHER arithmetic than the one the refine ranks
+// on (nais_pair_table_bound: the 3-product table under the fp16x6 refine):
+//   eta: every exact e lies in e~ [1 - eta, 1 + eta] of the tabled e~ (so in
+//        [e^ (1 - eta), e^ (1 + 2^-7)(1 + eta)] of its truncation e^),
+//   ds:  |s~ - s| <= ds for the two h . t values, absolute (s can cancel to nothing),
+// hence |e s - es~| <= (2^-7 + eta2) |es~| + e^ (1 + 2^-7)(1 + eta) ds per term, eta2 = 1.02 eta +
+// 2^-21 (eta on a |e~ s~| that is up to (1 + 2^-7) |es~|, and the two fp32 products' roundings).
+// Zeros: the bounds of the split16 route, bit for bit.
+struct Widen {
+  float eta, eta2, ds;
+};
+__device__ __forceinline__ Widen load_widen(const float* __restrict__ widen) {
+  Widen w{0.f, 0.f, 0.f};
+  if (widen) {
+    w.eta = widen[0];
+    w.ds = widen[1];
+    w.eta2 = w.eta > 0.f ? w.eta * 1.02f + 0x1p-21f : 0.f;
+  }
+  return w;
+}
+__device__ __forceinline__ Bounds make_bounds(float S, float N, float A, int64_t hl, float beta,
+                                              const Widen& w) {
   Bounds b;
   const float g = (float)hl * 0x1p-23f + 0x1p-20f;
   const float tiny = (float)hl * 0x1p-126f;   // truncation below the normal range (absolute)
-  b.slo = S * (1.f - 3.f * g);
-  b.shi = S * (1.f + 0x1p-7f) * (1.f + 3.f * g) + tiny;
-  const float rn = (0x1p-7f + 4.f * g) * A + tiny;
+  b.slo = S * (1.f - 3.f * g) * (1.f - w.eta);
+  b.shi = S * (1.f + 0x1p-7f) * (1.f + 3.f * g) * (1.f + w.eta) + tiny;
+  const float rn = (0x1p-7f + 4.f * g + w.eta2) * A + (tiny + S * (1.f + 0x1p-7f) * (1.f + w.eta) * w.ds);
   b.nlo = N - rn;
   b.nhi = N + rn;
   if (beta == 0.5f) {
@@ -647,11 +669,12 @@ __device__ __forceinline__ float lower_score(const Bounds& b) {
 // widened by 2^-17 to cover them and the accurate path's own rounding) is below L, the logit under
 // which the accurate upper score stays below the k-th key's score (lthr_of). beta == 0.5 only
 // (else L = -inf: no pruning); NaN anywhere keeps the candidate.
-__device__ __forceinline__ bool may_reach(float S, float N, float A, int64_t hl, float L) {
+__device__ __forceinline__ bool may_reach(float S, float N, float A, int64_t hl, float L, const Widen& w) {
   const float g = (float)hl * 0x1p-23f + 0x1p-20f;
   const float tiny = (float)hl * 0x1p-126f;
-  const float nhi = N + ((0x1p-7f + 4.f * g) * A + tiny);
-  const float sd = nhi >= 0.f ? S * (1.f - 3.f * g) : S * (1.f + 0x1p-7f) * (1.f + 3.f * g) + tiny;
+  const float nhi = N + ((0x1p-7f + 4.f * g + w.eta2) * A + (tiny + S * (1.f + 0x1p-7f) * (1.f + w.eta) * w.ds));
+  const float sd = nhi >= 0.f ? S * (1.f - 3.f * g) * (1.f - w.eta)
+                              : S * (1.f + 0x1p-7f) * (1.f + 3.f * g) * (1.f + w.eta) + tiny;
   float l = nhi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(sd));
   l += fabsf(l) * 0x1p-17f;
   return !(l < L);
@@ -728,11 +751,13 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
                        float beta, int k, unsigned long long* __restrict__ lokeys,
                        int32_t* __restrict__ locount, unsigned long long* __restrict__ surv,
                        int32_t* __restrict__ scount, int cap, const int32_t* __restrict__ erows,
-                       const int64_t* __restrict__ spans, int32_t* __restrict__ work) {
+                       const int64_t* __restrict__ spans, int32_t* __restrict__ work,
+                       const float* __restrict__ widen) {
   __shared__ unsigned long long lk[GW][BK_LDS];
   __shared__ uint32_t hm[GW][BSTRIPE / 32];   // history POIs of this block, one bit per column
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   constexpr int GQ = 4;
+  const Widen wd = load_widen(widen);
   int64_t qnext = 0, qend = 0;
   for (int64_t it = 0;; ++it) {
   int64_t slot;
@@ -813,9 +838,9 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
       if (hl == 0) {   // exact: logit 0 -> 0.5 for every candidate
         live |= 1u << q;
         ho[q] = lo_[q] = ord_f32_p(0.5f);
-      } else if (may_reach(S[q], N[q], A[q], hl, Lthr)) {
+      } else if (may_reach(S[q], N[q], A[q], hl, Lthr, wd)) {
         live |= 1u << q;
-        const Bounds b = make_bounds(S[q], N[q], A[q], hl, beta);
+        const Bounds b = make_bounds(S[q], N[q], A[q], hl, beta, wd);
         ho[q] = b.ok ? ord_f32_p(upper_score(b)) : 0xFFFFFFFFu;
         if (b.ok && key_of(ho[q], q) > thr) lo_[q] = ord_f32_p(lower_score(b));
       }
@@ -1041,6 +1066,385 @@ pair_refine_topk_kernel(const uint2* __restrict__ X, int64_t bstride, int64_t ld
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// On-demand exact refine (nais_pair_refine_topk_exact): phase 2 without the resident ex tables.
+// The (e, e*s) pair of (history item j, survivor c) is RECOMPUTED, with the fp32 bits the fp16x6
+// pair table (catalog_score_x6n_kernel, nais_kernels.hip) writes for that (row, column) in the
+// same job. A column of an MFMA result depends only on that column's B operand, the A operand
+// and the K order, so a pair's value is reproducible outside its table tile once every operand is
+// split under the scale the table kernel used: S_A / S_h per item row and S_t per column, which
+// pair_scales_kernel (nais_pair_scales) writes for the job's geometry. Power-of-two products
+// (S b1, w2 / S) are exact, so they are formed per lane. Everything else repeats that kernel:
+// A = (S_A W1) (.) h_j split into three f16 pieces, the six-product order (mfma16n_pieces), K-steps
+// in order from acc = S b1, the w2 . ReLU chain over the rows of a lane group and the hidden
+// blocks, the lane-group tree ((g0 + g2) + (g1 + g3)), expf, and s = h_j . t_c from the s tile's
+// arithmetic (pieces of S_h h_j against the same candidate pieces, / (S_h S_t)).
+// NAIS_basic, one hidden slice (H <= 64), D in {32, 64}: the shapes nais_pair_scales accepts.
+struct ExactModel {
+  const float* eh;
+  const float* et;
+  const float* w1;
+  const float* b1;
+  const float* w2;
+  int32_t H;
+};
+constexpr int EX_B = 32;          // candidates per batch: two 16-column MFMA blocks, as a table wave tile
+constexpr int EX_SVP = 17;        // s image pitch: [candidate][16 items]
+
+template <int D, int MB>
+struct ExactWave {                // a wave's W1 registers: row 16 m + (lane & 15), dims 32 s + 8 (lane >> 4) ..
+  static constexpr int KS = D / 32, HP = MB * 16;
+  float wv[MB][KS][8];            // scaled by SAcur (exact powers of two, as the table kernel rescales)
+  float SAcur;
+  __device__ __forceinline__ void load(const ExactModel& md) {
+    const int lane = threadIdx.x & 63, grp = lane >> 4, l16 = lane & 15;
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int s = 0; s < KS; ++s)
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+          const int i = 16 * m + l16;
+          wv[m][s][x] = i < md.H ? md.w1[(int64_t)i * D + 32 * s + 8 * grp + x] : 0.f;
+        }
+    SAcur = 1.f;
+  }
+};
+
+// [b1 | w2] by hidden unit (zero past H) into the workgroup's LDS; the caller barriers
+template <int HP>
+__device__ __forceinline__ void exact_stage_epi(const ExactModel& md, float* eimg) {
+  for (int f = threadIdx.x; f < 2 * HP; f += blockDim.x) {
+    const int i = f % HP;
+    eimg[f] = i < md.H ? (f < HP ? md.b1[i] : md.w2[i]) : 0.f;
+  }
+}
+
+// One batch: cand[0 .. 32) (this wave's LDS, published by the caller) holds the candidates' POI
+// ids (every one a valid row of embed_target). For each of the hl items item_at(j, id, row) yields (lanes ask for
+// different j), in order, sink(j, e, e * s, keep) runs with the pair's values for the candidate
+// this lane owns after the lane-group reduction -- candidate 16 (lane >> 5) + (lane & 15) of the
+// batch (lane groups 0 / 1 and 2 / 3 hold the same) -- and keep = the item is not that candidate.
+template <int D, int MB, class ItemAt, class Sink>
+__device__ __forceinline__ void pair_exact_batch(const ExactModel& md, ExactWave<D, MB>& ww,
+                                                 const float* __restrict__ eimg, float* __restrict__ svt,
+                                                 const float* __restrict__ rowsc,
+                                                 const float* __restrict__ colsc, int64_t col0,
+                                                 const uint32_t* cand, int64_t hl, ItemAt item_at, Sink sink) {
+  constexpr int KS = D / 32, HP = MB * 16;
+  const int lane = threadIdx.x & 63, grp = lane >> 4, l16 = lane & 15;
+  half8 tb[2][KS][3];
+  float Stn[2];
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+    const int64_t c = cand[16 * nb + l16];
+    const float St = colsc[c - col0];
+    Stn[nb] = St;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      const float* src = md.et + c * D + 32 * s + 8 * grp;
+      const float4 v0 = reinterpret_cast<const float4*>(src)[0];
+      const float4 v1 = reinterpret_cast<const float4*>(src)[1];
+      float x[8] = {v0.x * St, v0.y * St, v0.z * St, v0.w * St, v1.x * St, v1.y * St, v1.z * St, v1.w * St};
+      split_pieces<3>(x, tb[nb][s]);
+    }
+  }
+  const int own = 16 * (lane >> 5) + l16;
+  const int32_t cown = (int32_t)cand[own];
+  for (int64_t j0 = 0; j0 < hl; j0 += 16) {
+    const int jn = (int)std::min<int64_t>(16, hl - j0);   // wave-uniform
+    // lane l16 of every group: item j0 + l16 (its id, the scales of its table row)
+    int64_t id = 0;
+    int32_t row = 0;
+    const bool ok = l16 < jn;
+    if (ok) item_at(j0 + l16, id, row);
+    const float SA_m = ok ? rowsc[2 * (int64_t)row] : 1.f, Sh_m = ok ? rowsc[2 * (int64_t)row + 1] : 1.f;
+    {   // s tile: the 16 items (M) x the batch's candidates (N), kept as value / (S_h S_t)
+      const float* hrow = md.eh + id * D;
+      floatx4 sacc[2] = {floatx4{0.f, 0.f, 0.f, 0.f}, floatx4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const float* hp = hrow + 32 * s + 8 * grp;
+        const float4 h0 = *reinterpret_cast<const float4*>(hp);
+        const float4 h1 = *reinterpret_cast<const float4*>(hp + 4);
+        float x[8];
+        x[0] = ok ? h0.x * Sh_m : 0.f; x[1] = ok ? h0.y * Sh_m : 0.f;
+        x[2] = ok ? h0.z * Sh_m : 0.f; x[3] = ok ? h0.w * Sh_m : 0.f;
+        x[4] = ok ? h1.x * Sh_m : 0.f; x[5] = ok ? h1.y * Sh_m : 0.f;
+        x[6] = ok ? h1.z * Sh_m : 0.f; x[7] = ok ? h1.w * Sh_m : 0.f;
+        half8 hpc[3];
+        split_pieces<3>(x, hpc);
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) sacc[nb] = mfma16n_pieces(hpc, tb[nb][s], sacc[nb]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float Sh_i = __shfl(Sh_m, 4 * grp + r);
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          const float invShSt = 1.f / (Sh_i * Stn[nb]);
+          svt[(16 * nb + l16) * EX_SVP + 4 * grp + r] = sacc[nb][r] * invShSt;
+        }
+      }
+    }
+    wave_lds_sync();
+    for (int i = 0; i < jn; ++i) {
+      const float SA = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, SA_m), i));
+      const int32_t idi = __builtin_amdgcn_readlane((int32_t)id, i);   // POI ids fit 32 bits
+      if (SA != ww.SAcur) {   // wave-uniform: rescale the W1 registers (exact power-of-two ratio)
+        const float rs = SA / ww.SAcur;
+#pragma unroll
+        for (int m = 0; m < MB; ++m)
+#pragma unroll
+          for (int s = 0; s < KS; ++s)
+#pragma unroll
+            for (int x = 0; x < 8; ++x) ww.wv[m][s][x] *= rs;
+        ww.SAcur = SA;
+      }
+      const float* hr = md.eh + (int64_t)idi * D + 8 * grp;
+      float4 hv[KS][2];
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        hv[s][0] = *reinterpret_cast<const float4*>(hr + 32 * s);
+        hv[s][1] = *reinterpret_cast<const float4*>(hr + 32 * s + 4);
+      }
+      float Sacc[2], invS[2], t[2] = {0.f, 0.f};
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        Sacc[nb] = SA * Stn[nb];
+        invS[nb] = 1.f / Sacc[nb];
+      }
+#pragma unroll
+      for (int m = 0; m < MB; ++m) {
+        const float4 b4 = *reinterpret_cast<const float4*>(eimg + 16 * m + 4 * grp);
+        const float4 w4 = *reinterpret_cast<const float4*>(eimg + HP + 16 * m + 4 * grp);
+        floatx4 acc[2];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {   // the accumulators start at S * b1
+          acc[nb][0] = b4.x * Sacc[nb]; acc[nb][1] = b4.y * Sacc[nb];
+          acc[nb][2] = b4.z * Sacc[nb]; acc[nb][3] = b4.w * Sacc[nb];
+        }
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const float* w = ww.wv[m][s];
+          float a[8];
+          a[0] = w[0] * hv[s][0].x; a[1] = w[1] * hv[s][0].y; a[2] = w[2] * hv[s][0].z; a[3] = w[3] * hv[s][0].w;
+          a[4] = w[4] * hv[s][1].x; a[5] = w[5] * hv[s][1].y; a[6] = w[6] * hv[s][1].z; a[7] = w[7] * hv[s][1].w;
+          half8 pc[3];
+          split_pieces<3>(a, pc);
+          acc[0] = mfma16n_pieces(pc, tb[0][s], acc[0]);
+          acc[1] = mfma16n_pieces(pc, tb[1][s], acc[1]);
+        }
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {   // w2 / S . ReLU, the rows of this lane group in order
+          t[nb] = __builtin_fmaf(w4.x * invS[nb], relu_bits(acc[nb][0]), t[nb]);
+          t[nb] = __builtin_fmaf(w4.y * invS[nb], relu_bits(acc[nb][1]), t[nb]);
+          t[nb] = __builtin_fmaf(w4.z * invS[nb], relu_bits(acc[nb][2]), t[nb]);
+          t[nb] = __builtin_fmaf(w4.w * invS[nb], relu_bits(acc[nb][3]), t[nb]);
+        }
+      }
+      // the lane groups' partials: groups {g, g + 2}, then all four (the table kernel's tail)
+      const auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(t[0]), __float_as_uint(t[1]), false, false);
+      const float q = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
+      const auto r2 = __builtin_amdgcn_permlane16_swap(__float_as_uint(q), __float_as_uint(q), false, false);
+      const float a = __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
+      const float sv = svt[own * EX_SVP + i];
+      const bool keep = idi != cown;
+      const float e = expf(a) * (keep ? 1.f : 0.f);
+      float es = e * sv;
+      asm volatile("" : "+v"(es));   // the rounded product, as the table stores it: never fused into a sum
+      sink(j0 + i, e, es, keep);
+    }
+    wave_lds_sync();   // the next chunk's s image after this chunk's readers
+  }
+}
+
+template <int D, int MB>
+__global__ void __launch_bounds__(GW * 64, 2)
+pair_refine_exact_kernel(ExactModel md, const float* __restrict__ rowsc, const float* __restrict__ colsc,
+                         const int32_t* __restrict__ rowmap, const int64_t* __restrict__ indptr,
+                         const int64_t* __restrict__ indices, const int32_t* __restrict__ users,
+                         int32_t nusers, int64_t col0, int64_t cols, float beta, int k,
+                         const unsigned long long* __restrict__ lokeys, const int32_t* __restrict__ locount,
+                         const unsigned long long* __restrict__ surv, const int32_t* __restrict__ scount,
+                         int cap, const unsigned long long* __restrict__ tau_in,
+                         unsigned long long* __restrict__ keys, int32_t* __restrict__ kcount,
+                         int32_t* __restrict__ nan_count, int32_t* __restrict__ stats,
+                         const int32_t* __restrict__ erows) {
+  constexpr int HP = MB * 16;
+  __shared__ unsigned long long lk[GW][RF_LDS];
+  __shared__ uint32_t cb[GW][128];   // pending candidate columns (relative to col0)
+  __shared__ unsigned long long ck[GW][RF_CAND];   // kept survivors' upper keys, sorted
+  __shared__ __attribute__((aligned(16))) float eimg[2 * HP];
+  __shared__ float svt[GW][EX_B * EX_SVP];
+  __shared__ uint32_t bcand[GW][EX_B];   // the batch's candidates (POI ids)
+  exact_stage_epi<HP>(md, eimg);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t slot = int64_t(blockIdx.x) * GW + w;
+  if (slot >= nusers) return;                // wave-uniform; no workgroup barriers below
+  const int64_t u = users[slot];
+  const int64_t hb = indptr[u], hl = indptr[u + 1] - hb;
+  const int cnt = locount[slot];
+  unsigned long long tau = cnt == k ? lokeys[slot * k + k - 1] : 0ull;
+  if (tau_in && tau_in[slot] > tau) tau = tau_in[slot];
+  const int sc = scount[slot];
+  unsigned long long* L = lk[w];
+  int nk = 0;             // the running exact list L[0 .. nk)
+  int nan = 0, refined = 0;
+  ExactWave<D, MB> ww;
+  ww.load(md);
+  const int own = 16 * (lane >> 5) + (lane & 15);
+  const bool owner = !((lane >> 4) & 1);   // lane groups 1 / 3 repeat 0 / 2
+  auto item_at = [&](int64_t j, int64_t& id, int32_t& row) __attribute__((always_inline)) {
+    id = indices[hb + j];
+    row = erows ? erows[hb + j] : rowmap[id];
+  };
+  // exact keys of the columns r of lanes 0 .. n - 1 (n <= 32, wave-uniform) -> merged into L
+  auto batch = [&](int64_t r, int n) __attribute__((always_inline)) {
+    if (lane < EX_B) bcand[w][lane] = (uint32_t)(col0 + (lane < n ? r : 0));   // past n: a column that exists
+    wave_lds_sync();
+    float Sa = 0.f, Na = 0.f;
+    bool in_hist = false;
+    pair_exact_batch<D, MB>(md, ww, eimg, svt[w], rowsc, colsc, col0, bcand[w], hl, item_at,
+                            [&](int64_t, float e, float es, bool keep) __attribute__((always_inline)) {
+                              Sa += e;      // es arrives rounded and opaque: a plain add, as the gathers'
+                              Na += es;
+                              in_hist |= !keep;
+                            });
+    const int64_t c = bcand[w][own];
+    const bool vown = owner && own < n;
+    wave_lds_sync();   // the next batch's candidates after this one's readers
+    unsigned long long kq[1] = {0ull};
+    uint32_t offer = 0;
+    if (vown && !in_hist) {
+      float logit = 0.f;   // empty history: logit 0
+      if (hl > 0) logit = Na / ((beta == 0.5f) ? sqrtf(Sa) : powf(Sa, beta));
+      float s = 1.0f / (1.0f + expf(-logit));
+      if (logit != logit) {
+        s = __builtin_nanf("");
+        ++nan;
+      }
+      kq[0] = score_key(s, c);
+      ++refined;
+      const unsigned long long lthr = nk == k ? L[k - 1] : 0ull;
+      if (kq[0] > lthr) offer = 1u;
+    }
+    wave_lds_sync();
+    nk = wave_merge_keys<1>(L, nk, kq, offer, k);
+  };
+  auto col_of = [&](unsigned long long v) __attribute__((always_inline)) {
+    return (int64_t)((0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFull)) - (uint32_t)col0);
+  };
+  // The batches come from one of three sources, through one loop (the batch body is large):
+  //   ALL     an overflowed user: every column of the range;
+  //   SORTED  the kept survivors (upper key >= tau) sorted by upper key in LDS: refined in that
+  //           order until the list's k-th exact key is above the next one's upper key (no
+  //           candidate after it can enter);
+  //   STREAM  more kept survivors than the LDS sorts: streamed unsorted through cb.
+  enum { ALL, SORTED, STREAM };
+  const unsigned long long* list = surv + slot * (int64_t)cap;
+  unsigned long long* C = ck[w];
+  int nkept = 0;
+  for (int i0 = 0; i0 < sc; i0 += 64) {
+    const bool in = i0 + lane < sc;
+    const unsigned long long v = in ? list[i0 + lane] : 0ull;
+    const bool keep = in && v >= tau;
+    const unsigned long long bal = __ballot(keep);
+    const int pos = nkept + __popcll(bal & ((1ull << lane) - 1ull));
+    if (keep && pos < RF_CAND) C[pos] = v;
+    nkept += __popcll(bal);
+  }
+  const int mode = sc < 0 ? ALL : (nkept <= RF_CAND ? SORTED : STREAM);
+  if (mode == SORTED) wave_sort_desc(C, nkept);
+  int64_t pos = 0;   // ALL: next column; SORTED: next kept survivor; STREAM: next list entry
+  int pend = 0;      // STREAM: cb[w][0 .. pend) pending
+  for (;;) {
+    int64_t r = 0;
+    int n = 0;   // the batch: lanes 0 .. n - 1
+    if (mode == ALL) {
+      if (pos >= cols) break;
+      r = pos + lane;
+      n = (int)std::min<int64_t>(EX_B, cols - pos);
+      pos += EX_B;
+    } else if (mode == SORTED) {
+      if (pos >= nkept || (nk == k && L[k - 1] > C[pos])) break;   // wave-uniform (LDS, synced by the merge)
+      n = (int)std::min<int64_t>(EX_B, nkept - pos);
+      r = col_of(lane < n ? C[pos + lane] : 0ull);
+      pos += EX_B;
+    } else {
+      while (pend < EX_B && pos < sc) {   // refill: pend stays below EX_B + 64
+        const bool in = pos + lane < sc;
+        const unsigned long long v = in ? list[pos + lane] : 0ull;
+        const bool keep = in && v >= tau;
+        const unsigned long long bal = __ballot(keep);
+        if (keep) cb[w][pend + __popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)col_of(v);
+        pend += __popcll(bal);
+        pos += 64;
+        wave_lds_sync();
+      }
+      if (pend == 0) break;
+      n = pend < EX_B ? pend : EX_B;
+      r = cb[w][lane & (EX_B - 1)];
+      const uint32_t rest = cb[w][EX_B + lane];
+      wave_lds_sync();
+      cb[w][lane] = rest;
+      pend -= n;
+      wave_lds_sync();
+    }
+    batch(r, n);
+  }
+  for (int i = lane; i < nk; i += 64) keys[slot * k + i] = L[i];
+  if (lane == 0) kcount[slot] = nk;
+  if (nan_count) {
+    for (int o = 32; o > 0; o >>= 1) nan += __shfl_xor(nan, o);
+    if (lane == 0 && nan) atomicAdd(nan_count, nan);
+  }
+  if (stats) {
+    for (int o = 32; o > 0; o >>= 1) refined += __shfl_xor(refined, o);
+    if (lane == 0) {
+      atomicAdd(stats, refined);
+      if (sc < 0) atomicAdd(stats + 1, 1);
+    }
+  }
+}
+
+// nais_pair_recompute: out_e / out_es [nr][nc] = the pair values of table rows rows[0 .. nr) x
+// columns rcols[0 .. nc) by pair_exact_batch -- the refine's arithmetic, one wave per 32 columns
+// (rows and columns outside the job's item list / column range are clamped into them)
+template <int D, int MB>
+__global__ void __launch_bounds__(64)
+pair_recompute_kernel(ExactModel md, const int64_t* __restrict__ items, const float* __restrict__ rowsc,
+                      const float* __restrict__ colsc, int64_t nitems, int64_t col0, int64_t cols,
+                      const int32_t* __restrict__ rows, int64_t nr, const int64_t* __restrict__ rcols, int64_t nc,
+                      float* __restrict__ out_e, float* __restrict__ out_es) {
+  constexpr int HP = MB * 16;
+  __shared__ __attribute__((aligned(16))) float eimg[2 * HP];
+  __shared__ float svt[EX_B * EX_SVP];
+  __shared__ uint32_t bcand[EX_B];
+  exact_stage_epi<HP>(md, eimg);
+  const int lane = threadIdx.x & 63;
+  const int64_t x0 = int64_t(blockIdx.x) * EX_B;
+  const int own = 16 * (lane >> 5) + (lane & 15);
+  const bool vown = !((lane >> 4) & 1) && x0 + own < nc;
+  const int64_t cq = rcols[std::min<int64_t>(x0 + (lane & (EX_B - 1)), nc - 1)];
+  if (lane < EX_B) bcand[lane] = (uint32_t)std::min<int64_t>(std::max<int64_t>(cq, col0), col0 + cols - 1);
+  __syncthreads();
+  ExactWave<D, MB> ww;
+  ww.load(md);
+  pair_exact_batch<D, MB>(md, ww, eimg, svt, rowsc, colsc, col0, bcand, nr,
+                          [&](int64_t j, int64_t& id, int32_t& row) __attribute__((always_inline)) {
+                            row = (int32_t)std::min<int64_t>(std::max<int64_t>(rows[j], 0), nitems - 1);
+                            id = items[row];
+                          },
+                          [&](int64_t j, float e, float es, bool) __attribute__((always_inline)) {
+                            if (vown) {
+                              out_e[j * nc + x0 + own] = e;
+                              out_es[j * nc + x0 + own] = es;
+                            }
+                          });
+}
+
 // keys -> (ids, scores) of the top-k lists; short lists padded with -1 / NaN and counted
 __global__ void topk_keys_finish_kernel(const unsigned long long* __restrict__ keys,
                                         const int32_t* __restrict__ kcount, int32_t n, int k,
@@ -1150,12 +1554,13 @@ int32_t nais_pair_gather_topk(const float* e, const float* es, int64_t ld, const
   return NAIS_OK;
 }
 
-int32_t nais_pair_bound_topk(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
-                             const int64_t* indptr, const int64_t* indices, const int32_t* users,
-                             int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
-                             uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv, int32_t* surv_count,
-                             int32_t surv_cap, const int32_t* entry_rows, const int64_t* spans,
-                             int32_t* work, void* stream) {
+int32_t nais_pair_bound_topk_widened(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
+                                     const int64_t* indptr, const int64_t* indices, const int32_t* users,
+                                     int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
+                                     uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv,
+                                     int32_t* surv_count, int32_t surv_cap, const int32_t* entry_rows,
+                                     const int64_t* spans, const float* widen, int32_t* work,
+                                     void* stream) {
   if (num_users < 0 || col0 < 0 || cols < 0 || ld < cols || k <= 0 || surv_cap < 64)
     return nais_internal_fail(NAIS_E_INVALID, "bad shape");
   if (k > BK_LDS - 256) return nais_internal_fail(NAIS_E_UNSUPPORTED, "k must be <= 256");
@@ -1179,11 +1584,22 @@ int32_t nais_pair_bound_topk(const uint32_t* hi, int64_t ld, const int32_t* rowm
                        indptr, indices, users, num_users, col0 + s0, std::min<int64_t>(BSTRIPE, cols - s0),
                        beta, (int)k, reinterpret_cast<unsigned long long*>(lo_keys), lo_count,
                        reinterpret_cast<unsigned long long*>(surv), surv_count, (int)surv_cap, entry_rows,
-                       spans, work);
+                       spans, work, widen);
     const int32_t rc = nais_internal_check_launch("pair_bound_topk_kernel");
     if (rc) return rc;
   }
   return NAIS_OK;
+}
+
+int32_t nais_pair_bound_topk(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
+                             const int64_t* indptr, const int64_t* indices, const int32_t* users,
+                             int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
+                             uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv, int32_t* surv_count,
+                             int32_t surv_cap, const int32_t* entry_rows, const int64_t* spans,
+                             int32_t* work, void* stream) {
+  return nais_pair_bound_topk_widened(hi, ld, rowmap, indptr, indices, users, num_users, col0, cols, beta,
+                                      k, lo_keys, lo_count, surv, surv_count, surv_cap, entry_rows, spans,
+                                      nullptr, work, stream);
 }
 
 int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
@@ -1212,6 +1628,88 @@ int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
                      reinterpret_cast<const unsigned long long*>(tau),
                      reinterpret_cast<unsigned long long*>(keys), kcount, nan_count, stats, entry_rows);
   return nais_internal_check_launch("pair_refine_topk_kernel");
+}
+
+namespace {
+// the exact refine's shapes: those nais_pair_scales accepts; (D, MB) as the x6n table kernel's
+int exact_model(const nais_params_t* p, ExactModel* md, int* D, int* MB) {
+  if (!p) return nais_internal_fail(NAIS_E_INVALID, "params is NULL");
+  if (p->variant != NAIS_VARIANT_BASIC || p->precision != NAIS_PRECISION_FP16X6 ||
+      (p->embed_dim != 32 && p->embed_dim != 64) || p->hidden <= 0 || p->hidden > 64 ||
+      p->item_dim != p->embed_dim || p->din != p->embed_dim)
+    return nais_internal_fail(NAIS_E_UNSUPPORTED,
+                              "exact refine: NAIS_basic at fp16x6, embed_dim 32 or 64, hidden <= 64");
+  if (!p->embed_history || !p->embed_target || !p->w1 || !p->b1 || !p->w2)
+    return nais_internal_fail(NAIS_E_INVALID, "missing parameter pointer");
+  *md = ExactModel{p->embed_history, p->embed_target, p->w1, p->b1, p->w2, p->hidden};
+  *D = p->embed_dim;
+  *MB = p->hidden <= 32 ? 2 : 4;
+  return NAIS_OK;
+}
+}  // namespace
+
+int32_t nais_pair_refine_topk_exact(const nais_params_t* params, const float* row_scales,
+                                    const float* col_scales, const int32_t* rowmap, const int64_t* indptr,
+                                    const int64_t* indices, const int32_t* users, int32_t num_users,
+                                    int64_t col0, int64_t cols, int32_t k, const uint64_t* lo_keys,
+                                    const int32_t* lo_count, const uint64_t* surv, const int32_t* surv_count,
+                                    int32_t surv_cap, const uint64_t* tau, uint64_t* keys, int32_t* kcount,
+                                    int32_t* nan_count, int32_t* stats, const int32_t* entry_rows,
+                                    void* stream) {
+  ExactModel md;
+  int D, MB;
+  const int rc = exact_model(params, &md, &D, &MB);
+  if (rc) return rc;
+  if (num_users < 0 || col0 < 0 || cols < 0 || k <= 0 || surv_cap < 64 || col0 + cols > params->num_pois)
+    return nais_internal_fail(NAIS_E_INVALID, "bad shape");
+  if (k > RF_LDS - 256) return nais_internal_fail(NAIS_E_UNSUPPORTED, "k must be <= 256");
+  if (col0 + cols > 0x7FFFFFFFll) return nais_internal_fail(NAIS_E_UNSUPPORTED, "POI ids must fit 31 bits");
+  if (num_users == 0) return NAIS_OK;
+  if (!rowmap || !indptr || !indices || !users || !lo_keys || !lo_count || !surv || !surv_count ||
+      !keys || !kcount || !row_scales || (cols > 0 && !col_scales))
+    return nais_internal_fail(NAIS_E_INVALID, "missing pointer");
+  const dim3 grid((unsigned)((num_users + GW - 1) / GW)), block(GW * 64);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define NAIS_EXACT_REFINE(D_, MB_)                                                                   \
+  hipLaunchKernelGGL((pair_refine_exact_kernel<D_, MB_>), grid, block, 0, st, md, row_scales,        \
+                     col_scales, rowmap, indptr, indices, users, num_users, col0, cols, params->beta, \
+                     (int)k, reinterpret_cast<const unsigned long long*>(lo_keys), lo_count,          \
+                     reinterpret_cast<const unsigned long long*>(surv), surv_count, (int)surv_cap,    \
+                     reinterpret_cast<const unsigned long long*>(tau),                                \
+                     reinterpret_cast<unsigned long long*>(keys), kcount, nan_count, stats, entry_rows)
+  if (D == 32 && MB == 2) NAIS_EXACT_REFINE(32, 2);
+  else if (D == 32) NAIS_EXACT_REFINE(32, 4);
+  else if (MB == 2) NAIS_EXACT_REFINE(64, 2);
+  else NAIS_EXACT_REFINE(64, 4);
+#undef NAIS_EXACT_REFINE
+  return nais_internal_check_launch("pair_refine_exact_kernel");
+}
+
+int32_t nais_pair_recompute(const nais_params_t* params, const int64_t* items, int64_t num_items,
+                            const float* row_scales, const float* col_scales, int64_t col0, int64_t cols,
+                            const int32_t* rows, int64_t num_rows, const int64_t* columns,
+                            int64_t num_columns, float* out_e, float* out_es, void* stream) {
+  ExactModel md;
+  int D, MB;
+  const int rc = exact_model(params, &md, &D, &MB);
+  if (rc) return rc;
+  if (num_items <= 0 || col0 < 0 || cols <= 0 || col0 + cols > params->num_pois || num_rows < 0 ||
+      num_columns < 0 || col0 + cols > 0x7FFFFFFFll || num_columns > 0x7FFFFFFFll * EX_B)
+    return nais_internal_fail(NAIS_E_INVALID, "bad shape");
+  if (num_rows == 0 || num_columns == 0) return NAIS_OK;
+  if (!items || !row_scales || !col_scales || !rows || !columns || !out_e || !out_es)
+    return nais_internal_fail(NAIS_E_INVALID, "missing pointer");
+  const dim3 grid((unsigned)((num_columns + EX_B - 1) / EX_B)), block(64);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define NAIS_EXACT_RECOMPUTE(D_, MB_)                                                                \
+  hipLaunchKernelGGL((pair_recompute_kernel<D_, MB_>), grid, block, 0, st, md, items, row_scales,    \
+                     col_scales, num_items, col0, cols, rows, num_rows, columns, num_columns, out_e, out_es)
+  if (D == 32 && MB == 2) NAIS_EXACT_RECOMPUTE(32, 2);
+  else if (D == 32) NAIS_EXACT_RECOMPUTE(32, 4);
+  else if (MB == 2) NAIS_EXACT_RECOMPUTE(64, 2);
+  else NAIS_EXACT_RECOMPUTE(64, 4);
+#undef NAIS_EXACT_RECOMPUTE
+  return nais_internal_check_launch("pair_recompute_kernel");
 }
 
 int32_t nais_pair_prior_table(const double* coords, int64_t num_pois, const int64_t* items,
