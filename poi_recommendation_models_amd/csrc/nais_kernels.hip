@@ -279,6 +279,15 @@ struct Epi<HB, false> {
   __device__ __forceinline__ float w2(int i) const { return pw[i]; }
 };
 
+// e * s rounded on its own, never contracted into an fma with the running sum (__fmul_rn is a plain
+// product to the compiler and contracts). The pair tables store this product, so every route sums
+// the same terms: where e |s| overflows (the product-overflow band) two terms of
+// opposite sign give inf - inf = NaN on the per-user kernels too, not the first term's saturation.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __device__ __forceinline__ float finish_logit(float S, float N, float beta, bool empty) {
   if (empty) return 0.f;  // sum over an empty history dim (model.py:79-88 with n == 0)
   const float den = (beta == 0.5f) ? sqrtf(S) : powf(S, beta);
@@ -399,7 +408,7 @@ catalog_score_kernel(DevParams p, const int64_t* __restrict__ indptr,
       }
       in_hist |= !keep;
       S += e;                                               // model.py:79
-      N += e * s;                                           // sum_j w_j (h_j . t) numerator
+      N += mul_rn(e, s);                                    // sum_j w_j (h_j . t) numerator
     }
   }
   if (tab.e) return;
@@ -492,7 +501,7 @@ forward_kernel(DevParams p, const int64_t* __restrict__ hist, int64_t b, int64_t
     const bool keep = hrow_ids[j] != tgt;
     const float e = expf(a) * (keep ? 1.f : 0.f);
     S += e;
-    N += e * s;
+    N += mul_rn(e, s);   // the rounded product, as in catalog_score_kernel
     if (PREFETCH && j + 1 < n) {
 #pragma unroll
       for (int q = 0; q < DH / 4; ++q) hcur[q] = hnext[q];
@@ -860,7 +869,7 @@ catalog_score_x3_kernel(DevParams p, const int64_t* __restrict__ indptr,
       }
       in_hist |= !keep;
       S += e;
-      N += e * sv;
+      N += mul_rn(e, sv);   // the rounded product the table holds (no fma contraction)
     }
   }
   if (tab.e) return;
@@ -1103,7 +1112,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
       } else {
         in_hist |= !keep;
         S += e;
-        N += e * sv;
+        N += mul_rn(e, sv);   // the rounded product the table holds (no fma contraction)
       }
     }
     };
@@ -1674,8 +1683,9 @@ catalog_score_x6n_kernel(DevParams p, const int64_t* __restrict__ indptr,
     const bool keep = hid[pj] != (int32_t)cout;
     const float e = expf(a) * (keep ? 1.f : 0.f);
     in_hist |= live && !keep;
+    const float es = mul_rn(e, sv);   // the table's value; summed as such (no fma contraction)
     S += live ? e : 0.f;
-    N += live ? e * sv : 0.f;
+    N += live ? es : 0.f;
     const int64_t row = (hbeg + j0 + pj) * tab.ld;
     const int off = (live && vout) ? (int)(cout - tab.col0) * 4 : (int)0x80000000;
     const __amdgpu_buffer_rsrc_t re = __builtin_amdgcn_make_buffer_rsrc(tab.e + row, (short)0, tab_bytes, 0x00020000);
@@ -1686,7 +1696,7 @@ catalog_score_x6n_kernel(DevParams p, const int64_t* __restrict__ indptr,
     // job 0.5968 / 0.5967 / 0.5966 s, base / nt / sc1 means of three interleaved runs, profiles/r5/nt)
     // Float tables: even lanes e, odd lanes e*s. Split16: even lanes the hi word (one v_perm_b32)
     // and e into the ex pair, odd lanes e*s into the pair's second word.
-    const uint32_t eb = __float_as_uint(e), sb = __float_as_uint(e * sv);
+    const uint32_t eb = __float_as_uint(e), sb = __float_as_uint(es);
     const int off2 = tab.ex ? (off < 0 ? off : 2 * off + (odd ? 4 : 0)) : (odd ? off : (int)0x80000000);
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_amdgcn_perm(sb, eb, tab.sel_e), re, odd ? (int)0x80000000 : off, 0, 0);
     __builtin_amdgcn_raw_buffer_store_b32(odd ? sb : eb, rs, off2, 0, 0);

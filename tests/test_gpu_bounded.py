@@ -60,7 +60,11 @@ def _same(a, b):
 
 @pytest.mark.parametrize("variant,precision,D,H", [("basic", "fp16x6", 64, 64), ("basic", "fp32", 32, 32),
                                                    ("basic", "fp16x3", 64, 64), ("basic", "fp16x6", 100, 40),
-                                                   ("region_distance", "fp16x6", 64, 64)])
+                                                   ("region_distance", "fp16x6", 64, 64),
+                                                   # the generic-shape table writer (nais_generic.hip;
+                                                   # D = 100 above is padded to 128 and runs x6n)
+                                                   ("basic", "fp16x6", 192, 192), ("basic", "fp16x6", 64, 320),
+                                                   ("basic", "fp32", 192, 192)])
 def test_split_tables_hold_the_float_bits(variant, precision, D, H):
     from poi_recommendation_models_amd import _capi
     P, J, W = 3000, 300, 512
@@ -94,7 +98,7 @@ def test_split_tables_hold_the_float_bits(variant, precision, D, H):
 
 
 @pytest.mark.parametrize("case", ["bench_like", "reference_init", "beta07", "k1_k256", "region_distance",
-                                  "fp32", "generic_shape"])
+                                  "fp32", "generic_shape", "generic_192"])
 def test_bounded_route_equals_exact_route(case):
     from poi_recommendation_models_amd.synthetic import make_checkins
     P, U, hmax, k, D, H = 12000, 1500, 200, 50, 64, 64
@@ -108,6 +112,8 @@ def test_bounded_route_equals_exact_route(case):
         D = H = 32
     elif case == "generic_shape":
         D, H = 100, 40
+    elif case == "generic_192":     # past the tuned tiles: the generic-shape kernels, a shorter job
+        P, U, D, H = 4000, 300, 192, 192
     variant = "region_distance" if case == "region_distance" else "basic"
     data = make_checkins(U, P, hmax, seed=11)
     m = _model(P, D, H, variant, **kw)

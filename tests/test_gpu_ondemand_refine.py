@@ -12,7 +12,9 @@ nais_pair_bound_topk_widened / nais_pair_refine_topk_exact / nais_pair_recompute
 3. Route equality: ids, score bits and NaN counts of the new route equal the exact route's
    (PAIR_BOUNDED off) and the split16 route's (PAIR_ONDEMAND_REFINE off) on whole jobs.
 4. Two gloo ranks on one GPU through sharding.distributed_topk_pairs give the single-process lists,
-   each rank on the new route."""
+   each rank on the new route.
+5. The widening cache (catalog.ondemand_widening) follows every writer of the parameters: in-place
+   ops, load_state_dict, optim.Adagrad and NAISTrainer."""
 import os
 import socket
 import tempfile
@@ -260,6 +262,74 @@ def test_eta_beyond_the_threshold_keeps_the_split16_route():
     m = _model(2000, 32, 32, emb_std=3.0)
     assert catalog.ondemand_widening(m)[1] > catalog.PAIR_ONDEMAND_ETA_MAX
     assert _run(m, data, 50, "ondemand")[3] == ["split16"]
+
+
+def _widening_bits(m):
+    from poi_recommendation_models_amd import catalog
+    w, eta, ds = catalog.ondemand_widening(m)
+    return w.cpu().numpy().view(np.uint32).copy(), eta, ds
+
+
+@pytest.mark.parametrize("writer", ["inplace", "load_state_dict", "adagrad", "trainer", "inplace_x8"])
+def test_widening_cache_follows_every_writer(writer):
+    """catalog.ondemand_widening caches (eta', delta_s) on the parameters' (data_ptr, version
+    counter); a stale hit is a soundness matter (bounds that no longer cover the pairs can drop a
+    winner), and the contract is that every writer bumps the counters -- the native optimizer and
+    the in-tree trainer write through raw device pointers. After each writer the cached value must
+    be the one a fresh computation gives, and the default route must still return the exact
+    route's lists. `inplace_x8` takes eta' across the gate: the route changes to split16."""
+    from poi_recommendation_models_amd import catalog, optim
+    from poi_recommendation_models_amd.synthetic import make_checkins
+    from test_gpu_train import _batch, _csr, _params, _trainer
+    from test_gpu_train import _model as _train_model
+    P, D, H = 1500, 64, 64
+    data = make_checkins(150, P, 40, seed=8)
+    m = _train_model(_params(P, D, H, seed=21)).eval()
+    m.precision = "fp16x6"
+    assert _run(m, data, 50, "ondemand")[3] == ["ondemand"]        # fills the cache
+    assert "_widen_cache" in m.__dict__
+    before = _widening_bits(m)
+    hist, tgt, labels = _batch(P, 40, 4, seed=3)
+    if writer in ("inplace", "inplace_x8"):
+        with torch.no_grad():
+            m.embed_history.weight.mul_(2)
+            if writer == "inplace_x8":
+                m.embed_history.weight.mul_(4)
+                m.embed_target.weight.mul_(8)
+    elif writer == "load_state_dict":
+        sd = {k: v.clone() for k, v in m.state_dict().items()}
+        for k in ("embed_history.weight", "embed_target.weight"):
+            sd[k] *= 2
+        m.load_state_dict(sd)
+    elif writer == "adagrad":
+        m.train()
+        o = optim.Adagrad(m.parameters(), lr=0.05)
+        for q in m.parameters():
+            q.grad = None
+        pred = m(torch.as_tensor(hist).to(DEV), torch.as_tensor(tgt).to(DEV))
+        m.loss_func(pred, torch.as_tensor(labels).to(DEV)).backward()
+        o.step()
+    else:
+        m.train()
+        tr = _trainer(m, _csr(3, P, 30, seed=4), lr=0.05)
+        tr.step(torch.as_tensor(hist).to(DEV), torch.as_tensor(tgt).to(DEV), torch.as_tensor(labels).to(DEV))
+        tr.finish()
+    m.eval()
+    torch.cuda.synchronize()
+    # the default route first, on whatever the cache now answers
+    new, exact = _run(m, data, 50, "ondemand"), _run(m, data, 50, "exact")
+    np.testing.assert_array_equal(new[0], exact[0])
+    np.testing.assert_array_equal(new[1].view(np.uint32), exact[1].view(np.uint32))
+    assert new[2] == exact[2]
+    cached = _widening_bits(m)
+    m.__dict__.pop("_widen_cache", None)
+    fresh = _widening_bits(m)
+    print(writer, "eta' %.3e -> %.3e, delta_s %.3e -> %.3e, route %s" % (before[1], fresh[1], before[2], fresh[2], new[3]))
+    assert cached[1] == fresh[1] and cached[2] == fresh[2]
+    np.testing.assert_array_equal(cached[0], fresh[0])              # the device array, bit for bit
+    assert (fresh[1], fresh[2]) != (before[1], before[2]) and not np.array_equal(fresh[0], before[0])
+    if writer == "inplace_x8":
+        assert fresh[1] > catalog.PAIR_ONDEMAND_ETA_MAX and new[3] == ["split16"], (fresh[1], new[3])
 
 
 def _dist_setup():
