@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 15   /* 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 16   /* 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -232,8 +232,10 @@ int32_t nais_gather_rows(const float* table, int64_t rows, int32_t dim,
  *                      resident round of workgroups takes (item group, column tile) or user slots
  *                      from this counter (zeroed by the call, stream-ordered) until they run out,
  *                      so a CU-masked stream whose CU count is not a multiple of the shader-engine
- *                      count still uses every CU (nais_pair_table: the 16x16x32 fp16x6 kernel
- *                      only; other shapes ignore it). Results are identical either way.
+ *                      count still uses every CU (the table calls: the 16x16x32 fp16x6 kernel
+ *                      and, since ABI 16, the item-side split-fp16 kernel -- precision fp16x3, and
+ *                      fp16x6 at embed_dim 16 -- for the variants without distance inputs; other
+ *                      shapes and precisions ignore it). Results are identical either way.
  *   nais_pair_gather_topk  the same sums and scores, but instead of score rows each user keeps a
  *                      running top-k: keys[slot*k ..] (uint64, sorted descending, kcount[slot]
  *                      valid; zero kcount before the first call) with key = ordered(score) << 32 |
@@ -327,6 +329,10 @@ int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
  *   nais_pair_table_bound  the hi words of nais_pair_table_split at precision fp16x3 (same layout
  *                      and bits), whatever params->precision says; no (e, e*s) pairs are stored.
  *                      Native embed widths with hidden <= 128 (NAIS_E_UNSUPPORTED otherwise).
+ *   nais_pair_table_bound_queued  (ABI 16) the same table with nais_pair_table's `work` counter
+ *                      (above; zeroed by the call, stream-ordered): the item-side 3-product kernel
+ *                      then runs as a work queue, so the table stream's CU count may be any number.
+ *                      Every word equals nais_pair_table_bound's, which is this call with work = NULL.
  *   nais_pair_bound_topk_widened  nais_pair_bound_topk with widen = {eta, delta_s} (device floats;
  *                      NULL or zeros: nais_pair_bound_topk exactly): every exact e lies within
  *                      [1 - eta, 1 + eta] of the e whose truncation the hi word holds, and the two
@@ -351,6 +357,11 @@ int32_t nais_pair_table_bound(const nais_params_t* params, const int64_t* items,
                               int64_t col0, int64_t cols, const int64_t* region_of,
                               const double* coords, const double* latlon_mat, uint32_t* hi,
                               int64_t ld, void* stream);
+int32_t nais_pair_table_bound_queued(const nais_params_t* params, const int64_t* items,
+                                     int64_t num_items, int64_t col0, int64_t cols,
+                                     const int64_t* region_of, const double* coords,
+                                     const double* latlon_mat, uint32_t* hi, int64_t ld,
+                                     int32_t* work, void* stream);
 int32_t nais_pair_bound_topk_widened(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
                                      const int64_t* indptr, const int64_t* indices, const int32_t* users,
                                      int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,

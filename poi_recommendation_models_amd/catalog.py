@@ -263,11 +263,25 @@ PAIR_TABLE_GATHER_FRAC = 0.0
 # fill the CUs that block b's last, partial round of workgroups leaves idle (1,564 workgroups of
 # one table block = 9.8 rounds over 160 CUs; one stream waits for the whole launch to drain).
 PAIR_TABLE_STREAMS = int(os.environ.get("NAIS_PAIR_TABLE_STREAMS", "2"))
-# Work-queue launches of the table (16x16x32 kernel) and fused-gather kernels (round 4): a resident
-# round of workgroups takes items from a counter, so a stream's CU count need not be a multiple of
-# the 32 shader engines (auto_table_cus then steps in PAIR_SPLIT_STEP CUs).
+# Work-queue launches of the table kernels (the 16x16x32 fp16x6 kernel; since ABI 16 the item-side
+# fp16x3 kernel, i.e. the 3-product bound table) and of the fused-gather kernels: a resident round
+# of workgroups takes items from a counter, so a stream's CU count need not be a multiple of the
+# 32 shader engines (auto_table_cus then steps in PAIR_SPLIT_STEP CUs, or in 2).
 PAIR_WORK_QUEUE = os.environ.get("NAIS_PAIR_WORK_QUEUE", "1") != "0"
 PAIR_SPLIT_STEP = 8
+# auto_table_cus, the queued 3-product bound table (x3b behind nais_pair_table_bound_queued) under
+# the bounded gather, fitted on config 4 (profiles/x3b_queue): the tables ran 347.8
+# ms busy on 164 CUs (57.0 CU-s for 2.46e14 f16 FLOP: 1.10e15 FLOP/s on the whole chip), and past
+# ~160 CUs their busy time stops falling (349.6 / 349.4 / 349.0 / 348.4 / 348.0 ms on 162 / 164 /
+# 166 / 168 / 170 CUs of one box, 374.7 / 368.3 / 364.0 / 360.5 / 359.9 / 359.8 on 152 / 156 / 158 /
+# 160 / 162 / 164 of another; the cause is not established) while the gathers' keeps rising
+# (30.0-30.4 CU-s on 88-96 CUs against the 28.7 of bounded_gather_cu_seconds, fitted on 66-80), so
+# the step is level from 160 to 164 table CUs (376.9 / 377.3 ms at 162 / 164) and longer from 166
+# (379.4, 168: 382.4). The linear table model cannot hold that plateau; the margin on the gather
+# side stands in for it and for the fit's shortfall, and puts the pick at 162.
+# One job on one device size: refit both when a second job or device is measured.
+X3Q_RATE = 1.10e15
+X3Q_GATHER_MARGIN = 1.14
 # Bounded gather + exact refine (round 6; include/nais.h nais_pair_bound_topk): the fused top-k
 # from split16 tables -- the gather streams only their hi halves (4 bytes per history entry and
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
@@ -383,7 +397,7 @@ def _ondemand_shape(model, prm):
 
 
 def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, work_queues=True,
-                   gather_bytes=8, k=None, users=None, products=None):
+                   gather_bytes=8, k=None, users=None, products=None, table_queue=False):
     """CUs for the table stream (the rest gather), in steps of ncu / 8 (counts off a multiple of 32
     leave a shader engine short and lose -- DESIGN.md, CU split), from a cost model fitted
     on config 4 and config 5 (profiles/r1/cfg5p/, re-fitted in round 3 on the fp16x6 tables:
@@ -396,8 +410,12 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     reads it too (8 more bytes per history entry and column).
 
     `products`: the table kernel's f16 products per fp32 product when it is not the model's own
-    precision (the 3-product bound table of PAIR_ONDEMAND_REFINE; x3b has no work queue, so the
-    split then moves in shader-engine steps).
+    precision (the 3-product bound table of PAIR_ONDEMAND_REFINE).
+
+    `table_queue`: the 3-product table of this job runs as a work queue (the x3b kernel behind
+    nais_pair_table_bound_queued, ABI 16). Only then, and with `work_queues`, does `products=3`
+    step in 2 CUs, at the table rate fitted on the queued sweep; without it the 3-product split
+    moves in shader-engine steps (a fixed grid), as every call before ABI 16 did.
 
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
@@ -419,11 +437,16 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     x6n = (PAIR_WORK_QUEUE and work_queues and products == 6 and D in (32, 64, 128) and H <= 128
            and not prior)
     step = min(PAIR_SPLIT_STEP, xcd) if x6n else xcd
+    # the 3-product bound table as a work queue (x3b, ABI 16) under the bounded gather
+    x3q = (PAIR_WORK_QUEUE and work_queues and table_queue and products == 3 and gather_bytes == 4
+           and D in (16, 32, 64, 128) and H <= 128 and not prior and not dist)   # no queue with distance inputs
     # round 4: 1.45e15 (config 4), 1.55e15 (config-5 shard); round 6: 1.47e15 -- the final tree's
     # config-4 tables ran 446.5 ms on 190 CUs (1.45e15 said 456.8), and 1.47e15 keeps every
     # measured best split: 190 / 190 / 186 / 180 at N = 1 / 2 / 4 / 8 (profiles/r6/split_n1,
     # split_world) and region_distance at 194 (profiles/r6/rd_split), where 1.45e15 chose 196
     rate = 1.47e15 if x6n else 1.25e15
+    if x3q:
+        rate = X3Q_RATE
     din_k = D + (2 if dist else 0)      # the width the kernels multiply (padded)
     t_tab = J * NC * 2.0 * H * din_k * products / (1.3e14 if products == 1 else rate)
     if x6n and dist:
@@ -442,7 +465,7 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
         # profiles/r6/bounded, split_ab), and 4-CU steps: 188 / 68 ran 471.4 ms against 476.9 /
         # 480.2 at 184 / 72 and 490.8 at 180 / 76 on one box (profiles/r6/split_ab)
         per_cu = 66e9
-        if x6n:
+        if x6n or x3q:
             # 2-CU steps: config 4 at 190 / 66 ran 476.2 / 476.8 / 478.6 ms against 482.4-482.5 at
             # 188 / 68, interleaved on one box (profiles/r6/split_n1); one rank of N = 2 at 190
             # 239.0 / 239.3 vs 240.5 / 240.9 at 188, N = 4 at 186 even with 184, config 2 at 234
@@ -453,6 +476,8 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
             # rank's narrow column shard (N = 8: best split 172-180 against 188 at N = 1,
             # profiles/r6/split_world) and short histories (config 2) pay more per byte
             per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k)
+        if x3q:
+            per_cu /= X3Q_GATHER_MARGIN
     cap = 7.5e12   # the memory side's rate for the gather, chip-wide
     best, best_t = ncu // 2, None
     for n in range((ncu // 4 + step - 1) // step * step, ncu - step + 1, step):
@@ -617,9 +642,11 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
         prior_flags = _capi.PRIOR_FINITE if _prior_entries_finite(pa, pb) else 0
     pr_of = {}   # column-block table -> its float64 pr_d table (prior only)
 
-    # work-queue counters (PAIR_WORK_QUEUE): one int32 per stream, each used stream-ordered; on
-    # only for a split off the shader-engine steps (config 4 at 152 / 104: 598 ms vs 607 at the
-    # classic 160 / 96; config-5 shard at 232 / 24: 17.3 s vs 18.2 at 224 / 32 -- profiles/r4/wq)
+    # work-queue counters (PAIR_WORK_QUEUE): one int32 per stream, each used stream-ordered (the
+    # launch zeroes its counter itself, behind the stream's previous launch). On for a split off
+    # the shader-engine steps (config 4 at 152 / 104: 598 ms vs 607 at the classic 160 / 96;
+    # config-5 shard at 232 / 24: 17.3 s vs 18.2 at 224 / 32 -- profiles/r4/wq) and, on the
+    # on-demand route, at every split (wq_on below)
     wq_slots = torch.zeros(8, dtype=torch.int32, device=dev) if PAIR_WORK_QUEUE else None
     wq_of = {}
     wq_on = [False]
@@ -636,9 +663,9 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
 
     def table(tab, c0, w, stream_):
         if isinstance(tab, tuple) and len(tab) == 1:   # on-demand refine: hi words alone, 3 products
-            _capi.check(lib.nais_pair_table_bound(prm, items.data_ptr(), J, c0, w, _capi.ptr(reg),
-                                                  _capi.ptr(cor), _capi.ptr(llm), tab[0].data_ptr(),
-                                                  ld, stream_), "nais_pair_table_bound")
+            _capi.check(lib.nais_pair_table_bound_queued(
+                prm, items.data_ptr(), J, c0, w, _capi.ptr(reg), _capi.ptr(cor), _capi.ptr(llm),
+                tab[0].data_ptr(), ld, wq(stream_), stream_), "nais_pair_table_bound_queued")
             return
         if isinstance(tab, tuple):   # the bounded route's split16 tables (hi words, ex pairs)
             _capi.check(lib.nais_pair_table_split(prm, items.data_ptr(), J, c0, w, _capi.ptr(reg),
@@ -777,9 +804,13 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
             table_cus = (auto_table_cus(model, J, NC, entries, ncu, prior is not None,
                                         J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
-                                        users=m, products=3 if ondm[0] else None)
+                                        users=m, products=3 if ondm[0] else None,
+                                        table_queue=ondm[0])
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
-            wq_on[0] = table_cus % max(1, ncu // 8) != 0
+            # the on-demand route runs its streams as queues on the engine grid too: config 4 at
+            # 160 table CUs ran level with 162 as a queue, 393.3 ms on the fixed grid against
+            # 375-377 queued (profiles/x3b_queue). Every other route keeps what it had.
+            wq_on[0] = table_cus % max(1, ncu // 8) != 0 or (ondm[0] and wq_both)
             if events is not None:
                 events.append(("table_cus", None, None, table_cus))
                 events.append(("block_cols", None, None, W))

@@ -72,7 +72,8 @@ struct TableOut {
   float* es = nullptr;
   int64_t ld = 0, col0 = 0, cols = 0, nitems = 0;
   int32_t gi = 0;
-  // work queue (x6n only): the launch's item counter, zeroed before it, and the item grid it covers
+  // work queue (x6n, x3b without distance inputs): the launch's item counter, zeroed before it,
+  // and the item grid it covers
   int32_t* work = nullptr;
   int32_t ngroups = 0, ntiles = 0;
   // the split16 form (nais_internal.h): e receives the hi words (sel_e = NAIS_SEL_HI, one
@@ -928,7 +929,9 @@ struct CfgB {
 };
 
 // NW = waves per workgroup (2 per SIMD at 8). D, H <= 64 pipeline the epilogue (CfgB::PIPE).
-template <int DH, int HB, int VAR, int NW, int NPC>
+// QUEUE: the work-queue form of pair-table mode (tab.work given); false compiles the work loop away,
+// so per-user mode and the fixed-grid tables keep the code they had before the queue existed.
+template <int DH, int HB, int VAR, int NW, int NPC, bool QUEUE = false>
 __global__ void __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW)   // >= 2 waves per SIMD per CU
 catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
                          const int64_t* __restrict__ indices, const int32_t* __restrict__ users,
@@ -955,18 +958,8 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   double* hco = reinterpret_cast<double*>(hid + JCB);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
-  int64_t hbeg, hlen;
-  if (tab.e) {   // pair-table mode: a group of tab.gi rows of the item list
-    hbeg = (int64_t)cat_user_slot() * tab.gi;
-    hlen = std::min<int64_t>(tab.gi, tab.nitems - hbeg);
-  } else {
-    const int64_t u = users[cat_user_slot()];
-    hbeg = indptr[u];
-    hlen = indptr[u + 1] - hbeg;
-  }
-  const int64_t c = tab.col0 + (int64_t)cat_tile() * CAND_PER_BLOCK + wave * 32 + (lane & 31);
-  const bool valid = c < p.P && (!tab.e || c < tab.col0 + tab.cols);
-  const int64_t cc = valid ? c : p.P - 1;
+  int32_t* wi_sh = reinterpret_cast<int32_t*>(red + 15);   // block_max_n uses red[0, NW)
+  static_assert(NW < 16, "the work item's LDS word sits behind the block reductions' slots");
 
   // ---- this thread's W1 values for the fragment entries it builds (fp32, unscaled)
   float wv[EPT][8];
@@ -996,52 +989,99 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     Eimg[f] = (i < p.H) ? (which == 0 ? p.b1[i] : p.w2[i]) : 0.f;
   }
 
-  // ---- candidate operand: t_c scaled by S_t (fp32 copy for h . t) and its fp16 hi/lo B fragments
-  float tv[DH];
-  {
-    const float* src = (REGION && hh) ? p.er + region_of[cc] * p.region_dim
-                                      : p.et + cc * p.item_dim + (REGION ? 0 : hh * DH);
-#pragma unroll
-    for (int q = 0; q < DH / 4; ++q) {
-      const float4 v = reinterpret_cast<const float4*>(src)[q];
-      tv[4 * q] = v.x;
-      tv[4 * q + 1] = v.y;
-      tv[4 * q + 2] = v.z;
-      tv[4 * q + 3] = v.w;
-    }
-  }
-  float tmax = 0.f;
-#pragma unroll
-  for (int k = 0; k < DH; ++k) tmax = fmaxf(tmax, fabsf(tv[k]));
-  tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
-  if constexpr (C::WLDS) {   // one scale for the wave's 32 candidates (its pieces reach 2^-39 of it)
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, o));
-  }
-  const float St = pow2_scale(tmax);
-  const float invSt = 1.f / St;
-  half8 tb[KS][NPC];
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    float x[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      tv[8 * s + e] *= St;
-      x[e] = tv[8 * s + e];
-    }
-    split_pieces<NPC>(x, tb[s]);
-  }
-  double clat = 0.0, clon = 0.0;
   DistW dw{0.f, 0.f, 0.f};
+  if (DIST) dw = load_distw<VAR>(p, hh);
+  float SAcur = 1.f;   // the W1 registers' current scale (rescaled per chunk, kept across work items)
+
+  // Work items: (item group, column tile) in pair-table mode, (user slot, column tile) otherwise.
+  // With tab.work (pair-table mode) the workgroup takes items from that counter until they run
+  // out, as x6n does: the grid is one resident round of workgroups, so the stream's CU count need
+  // not be a multiple of the 32 shader engines. Items are tile-major, so the candidate operands
+  // (tv, tb, St) usually carry over to the next item; the W1 registers, Wmax and the b1 / w2 image
+  // do not depend on the item at all. Without the counter: one item, the launch's fixed grid.
+  // The queue is a template instance of its own (QUEUE), launched only for a table with a counter
+  // and no distance inputs (the pipelined D = H = 64 distance instances sit at 256 VGPRs and the
+  // loop's carried state spilled there): the loop costs SGPRs, and some shapes a wave of occupancy.
+  // Across items the W1 registers keep the rounding of every rescale they went through: exact while
+  // W1 * S_A stays in fp32's normal range, which pow2_scale's clamp at 2^+-120 and operands outside
+  // 2^+-100 can break (denormal bits lost under one item's scale stay lost for the next, and a
+  // ratio of two clamped scales can overflow). A fixed-grid workgroup starts from the unscaled W1,
+  // so the two forms agree word for word only inside that range -- the range ondemand_widening's
+  // gate keeps the route to.
+  static_assert(!QUEUE || !DIST, "the work queue covers the variants without distance inputs");
+  int64_t wslot = cat_user_slot(), wtile = cat_tile(), cur_tile = -1;
+  int64_t c = 0;
+  bool valid = false;
+  float tv[DH];
+  half8 tb[KS][NPC];
+  float St = 1.f, invSt = 1.f;
+  double clat = 0.0, clon = 0.0;
   const double* llrow = nullptr;
-  if (DIST) {
-    if (coords) {
-      clat = coords[2 * cc];
-      clon = coords[2 * cc + 1];
-    } else {
-      llrow = latlon_mat + cc * p.P * 2;
+  do {   // QUEUE: until the counter runs out; otherwise once (`while (QUEUE)` below)
+  if constexpr (QUEUE) {   // the launch gives tab.work, tab.ngroups and tab.ntiles
+    __syncthreads();   // the previous item's readers of wi_sh, hrows, hid and the ring are done
+    if (tid == 0) *wi_sh = atomicAdd(tab.work, 1);
+    __syncthreads();
+    const int64_t wi = *wi_sh;   // block-uniform: every thread leaves the loop together
+    if (wi >= (int64_t)tab.ngroups * tab.ntiles) break;
+    wtile = wi / tab.ngroups;
+    wslot = wi % tab.ngroups;
+  }
+  int64_t hbeg, hlen;
+  if (tab.e) {   // pair-table mode: a group of tab.gi rows of the item list
+    hbeg = wslot * tab.gi;
+    hlen = std::min<int64_t>(tab.gi, tab.nitems - hbeg);
+  } else {
+    const int64_t u = users[wslot];
+    hbeg = indptr[u];
+    hlen = indptr[u + 1] - hbeg;
+  }
+  if (!QUEUE || wtile != cur_tile) {   // block-uniform
+    cur_tile = wtile;
+    c = tab.col0 + wtile * CAND_PER_BLOCK + wave * 32 + (lane & 31);
+    valid = c < p.P && (!tab.e || c < tab.col0 + tab.cols);
+    const int64_t cc = valid ? c : p.P - 1;
+    // ---- candidate operand: t_c scaled by S_t (fp32 copy for h . t) and its fp16 hi/lo B fragments
+    {
+      const float* src = (REGION && hh) ? p.er + region_of[cc] * p.region_dim
+                                        : p.et + cc * p.item_dim + (REGION ? 0 : hh * DH);
+#pragma unroll
+      for (int q = 0; q < DH / 4; ++q) {
+        const float4 v = reinterpret_cast<const float4*>(src)[q];
+        tv[4 * q] = v.x;
+        tv[4 * q + 1] = v.y;
+        tv[4 * q + 2] = v.z;
+        tv[4 * q + 3] = v.w;
+      }
     }
-    dw = load_distw<VAR>(p, hh);
+    float tmax = 0.f;
+#pragma unroll
+    for (int k = 0; k < DH; ++k) tmax = fmaxf(tmax, fabsf(tv[k]));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
+    if constexpr (C::WLDS) {   // one scale for the wave's 32 candidates (its pieces reach 2^-39 of it)
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) tmax = fmaxf(tmax, __shfl_xor(tmax, o));
+    }
+    St = pow2_scale(tmax);
+    invSt = 1.f / St;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      float x[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        tv[8 * s + e] *= St;
+        x[e] = tv[8 * s + e];
+      }
+      split_pieces<NPC>(x, tb[s]);
+    }
+    if (DIST) {
+      if (coords) {
+        clat = coords[2 * cc];
+        clon = coords[2 * cc + 1];
+      } else {
+        llrow = latlon_mat + cc * p.P * 2;
+      }
+    }
   }
 
   float S = 0.f, N = 0.f;
@@ -1224,7 +1264,6 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     tail(cur, ap, sd, true);
   };
 
-  float SAcur = 1.f;
   floatx16 acc2[2][HB];   // PIPE: the accumulators of even / odd chunk-local items
   for (j0 = 0; j0 < hlen; j0 += JCB) {
     const int jn = (int)std::min<int64_t>(JCB, hlen - j0);
@@ -1325,7 +1364,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
         step(std::false_type{}, std::true_type{}, ring, acc2[1], acc2[0], 0, prev, true);
     }
   }
-  if (tab.e) return;
+  if (tab.e) continue;   // the next work item, or out (to `while (QUEUE)`)
 
   const float logit = finish_logit(S, N, p.beta, hlen == 0);
   const bool isnan_ = logit != logit;
@@ -1337,6 +1376,8 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     const unsigned long long m = __ballot(valid && hh == 0 && !in_hist && isnan_);
     if (lane == 0 && m) atomicAdd(nan_count, (int32_t)__popcll(m));
   }
+  break;
+  } while (QUEUE);   // work items
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2765,7 +2806,8 @@ int launch_catalog_x3(const DevParams& d, const int64_t* indptr, const int64_t* 
 // shape it covers: D in {32, 64, 128}, H <= 256, every variant (the distance variants since round 5).
 // Round-4 A/B against x3b at config 4: standalone 512-column table block 2.179 -> 1.990 ms, the job
 // 623 -> 601 ms (profiles/r4/x6n); at D = H = 128 against the per-pair split kernel: config-5 direct
-// 6.35e7 -> 7.32e7 pairs/s (profiles/r4/d128). The A/B switch is gone; x3b keeps fp16x3.
+// 6.35e7 -> 7.32e7 pairs/s (profiles/r4/d128). The A/B switch is gone; x3b keeps fp16x3, in table
+// mode as a work queue too when the caller gives the counter (ABI 16, profiles/x3b_queue).
 template <int DH, int HB, int VAR, int NPC = 2>
 int launch_catalog_x3b(const DevParams& d, const int64_t* indptr, const int64_t* indices,
                        const int32_t* users, int nb, const int64_t* region_of, const double* coords,
@@ -2826,8 +2868,31 @@ int launch_catalog_x3b(const DevParams& d, const int64_t* indptr, const int64_t*
       attr_set = true;
     }
     dim3 grid = tab.e ? table_grid(tab, nb, NW * 32) : cat_grid(d.P, nb, NW * 32);
+    TableOut t = tab;
+    if constexpr (!VarT<VAR>::DIST) {
+      if (t.e && t.work) {   // work queue, as x6n above: one workgroup per CU of the stream's mask,
+        t.ngroups = (int32_t)grid.y;   // items tile-major, the counter zeroed stream-ordered here
+        t.ntiles = (int32_t)grid.x;
+        auto kq = catalog_score_x3b_kernel<DH, HB, VAR, NW, NPC, true>;
+        static bool attr_set_q = false;
+        if (!attr_set_q) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kq),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+          attr_set_q = true;
+        }
+        const int ncu = nais_internal_stream_cus(stream);
+        if (ncu <= 0) return fail(NAIS_E_HIP, "device attributes");
+        grid = dim3((unsigned)std::min<int64_t>((int64_t)grid.x * grid.y, ncu), 1, 1);
+        if (hipMemsetAsync(t.work, 0, sizeof(int32_t), stream) != hipSuccess)
+          return fail(NAIS_E_HIP, "hipMemsetAsync(work)");
+        hipLaunchKernelGGL(kq, grid, dim3(NW * 64), lds, stream, d, indptr, indices, users, region_of,
+                           coords, latlon_mat, scores, ld, nan_count, t);
+        return check_launch("catalog_score_x3b_kernel (queue)");
+      }
+    }
+    t.work = nullptr;   // the fixed grid
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, stream, d, indptr, indices, users, region_of,
-                       coords, latlon_mat, scores, ld, nan_count, tab);
+                       coords, latlon_mat, scores, ld, nan_count, t);
     return check_launch("catalog_score_x3b_kernel");
   }
 }
@@ -3142,8 +3207,17 @@ int32_t nais_pair_table_bound(const nais_params_t* params, const int64_t* items,
                               int64_t col0, int64_t cols, const int64_t* region_of,
                               const double* coords, const double* latlon_mat, uint32_t* hi,
                               int64_t ld, void* stream) {
+  return nais_pair_table_bound_queued(params, items, num_items, col0, cols, region_of, coords,
+                                      latlon_mat, hi, ld, nullptr, stream);
+}
+
+int32_t nais_pair_table_bound_queued(const nais_params_t* params, const int64_t* items,
+                                     int64_t num_items, int64_t col0, int64_t cols,
+                                     const int64_t* region_of, const double* coords,
+                                     const double* latlon_mat, uint32_t* hi, int64_t ld,
+                                     int32_t* work, void* stream) {
   return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
-                         reinterpret_cast<float*>(hi), nullptr, ld, nullptr, stream, false, true);
+                         reinterpret_cast<float*>(hi), nullptr, ld, work, stream, false, true);
 }
 
 int32_t nais_pair_scales(const nais_params_t* params, const int64_t* items, int64_t num_items,
