@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 16   /* 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 17   /* 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -333,6 +333,16 @@ int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
  *                      (above; zeroed by the call, stream-ordered): the item-side 3-product kernel
  *                      then runs as a work queue, so the table stream's CU count may be any number.
  *                      Every word equals nais_pair_table_bound's, which is this call with work = NULL.
+ *   nais_pair_table_bound1_queued  (ABI 17) hi words of the one-product-logit table; s as in
+ *                      nais_pair_table_bound. The attention logit of each pair takes one f16
+ *                      product per term (hi * hi of the same scaled operands) instead of three, so
+ *                      e = exp(a) carries a relative error near 2^-10 of the logit's terms where
+ *                      nais_pair_table_bound's carries 2^-21; s = h . t keeps the three products
+ *                      and the bits it has there, and e * s is their fp32 product. Same arguments;
+ *                      work = NULL selects the fixed grid, whose words equal the queued ones. The
+ *                      gather must widen by the one-product bound (catalog.ondemand_widening with
+ *                      products = 1). NAIS_basic, embed_dim 32 or 64, hidden <= 64
+ *                      (NAIS_E_UNSUPPORTED otherwise).
  *   nais_pair_bound_topk_widened  nais_pair_bound_topk with widen = {eta, delta_s} (device floats;
  *                      NULL or zeros: nais_pair_bound_topk exactly): every exact e lies within
  *                      [1 - eta, 1 + eta] of the e whose truncation the hi word holds, and the two
@@ -362,6 +372,11 @@ int32_t nais_pair_table_bound_queued(const nais_params_t* params, const int64_t*
                                      const int64_t* region_of, const double* coords,
                                      const double* latlon_mat, uint32_t* hi, int64_t ld,
                                      int32_t* work, void* stream);
+int32_t nais_pair_table_bound1_queued(const nais_params_t* params, const int64_t* items,
+                                      int64_t num_items, int64_t col0, int64_t cols,
+                                      const int64_t* region_of, const double* coords,
+                                      const double* latlon_mat, uint32_t* hi, int64_t ld,
+                                      int32_t* work, void* stream);
 int32_t nais_pair_bound_topk_widened(const uint32_t* hi, int64_t ld, const int32_t* rowmap,
                                      const int64_t* indptr, const int64_t* indices, const int32_t* users,
                                      int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -35,7 +35,7 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_topk_merge_f64", "nais_train_ucache_size", "nais_pair_table_split",
            "nais_pair_bound_topk", "nais_pair_refine_topk", "nais_pair_table_bound",
            "nais_pair_bound_topk_widened", "nais_pair_scales", "nais_pair_refine_topk_exact",
-           "nais_pair_recompute", "nais_pair_table_bound_queued")
+           "nais_pair_recompute", "nais_pair_table_bound_queued", "nais_pair_table_bound1_queued")
 
 
 class NaisDotTables(ctypes.Structure):
@@ -241,6 +241,8 @@ def load(path: str | None = None):
     lib.nais_pair_table_bound_queued.restype = i32
     lib.nais_pair_table_bound_queued.argtypes = [ctypes.POINTER(NaisParams), vp, i64, i64, i64, vp, vp, vp,
                                                  vp, i64, vp, vp]
+    lib.nais_pair_table_bound1_queued.restype = i32
+    lib.nais_pair_table_bound1_queued.argtypes = lib.nais_pair_table_bound_queued.argtypes
     lib.nais_pair_bound_topk_widened.restype = i32
     lib.nais_pair_bound_topk_widened.argtypes = [vp, i64, vp, vp, vp, vp, i32, i64, i64, f32, i32, vp, vp,
                                                  vp, vp, i32, vp, vp, vp, vp, vp]

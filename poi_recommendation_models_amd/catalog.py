@@ -282,6 +282,18 @@ PAIR_SPLIT_STEP = 8
 # One job on one device size: refit both when a second job or device is measured.
 X3Q_RATE = 1.10e15
 X3Q_GATHER_MARGIN = 1.14
+# The queued one-product-logit bound table (ABI 17), fitted the same way on config 4
+# (profiles/x1b): where the tables bound the step they took 34-35.5 CU-s (311 / 296 /
+# 287 ms busy on 114 / 116 / 118 CUs; 217 ms on 162) for 8.19e13 f16 FLOP -- one product per logit
+# term -- or 6.0e14 FLOP/s on the whole chip. The gathers, now the longer stream, do not scale
+# with their CUs as the linear model has it: 309.3 / 295.3 / 288.1 / 280.6 / 278.9 ms busy on 94 / 104 /
+# 116 / 128 / 136 CUs, about 211 ms + 9.3 CU-s / CUs, so past ~120 gather CUs each one buys little while
+# every CU the tables lose costs them 2.4 ms. The step is lowest at 120 / 136 (309.9-310.3 ms), level at
+# 122 (310.2-310.6) and 124, and rises steeply below (118: 315.3-316.3, 116: 324-327, 114: 340);
+# the margin stands in for the gathers' saturation and puts the pick at 122, one step off the
+# cliff. One job on one device size, as above.
+X1Q_RATE = 6.0e14
+X1Q_GATHER_MARGIN = 1.34
 # Bounded gather + exact refine (round 6; include/nais.h nais_pair_bound_topk): the fused top-k
 # from split16 tables -- the gather streams only their hi halves (4 bytes per history entry and
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
@@ -306,6 +318,13 @@ PAIR_BOUNDED = True
 # premise is gone); "0" keeps the split16 route (A/B).
 PAIR_ONDEMAND_REFINE = os.environ.get("NAIS_PAIR_ONDEMAND_REFINE", "1") != "0"
 PAIR_ONDEMAND_ETA_MAX = 2.0 ** -9
+# One f16 product per logit term in the bound table (nais_pair_table_bound1_queued, ABI 17; DESIGN.md
+# (d) "One product per logit term"): a third of the table's matrix work, a wider eta' (config 4:
+# 5.65e-3 against 4.2e-4). Taken when eta'_1 <= 2^-7 -- a design limit like the 2^-9 above: there the
+# interval has at most doubled against the split16 route's 2^-7 -- else the three-product table under
+# its own rule, else split16. "0" forces the three-product form (A/B).
+PAIR_ONDEMAND_ONE_PRODUCT = os.environ.get("NAIS_PAIR_ONDEMAND_ONE_PRODUCT", "1") != "0"
+PAIR_ONDEMAND_ETA1_MAX = 2.0 ** -7
 PAIR_SURV_CAP = 1024            # survivor keys per user (compacted by the current bound when full)
 # the bounded gather / refine get each CSR entry's table row and each slot's history span (ABI 14:
 # shorter chains of dependent loads); "0" passes NULL (A/B only). Per gather launch 2.272 -> 2.224
@@ -333,7 +352,7 @@ def bounded_gather_cu_seconds(entries, NC, users, k):
     return entries * NC * 4.0 / 90.4e9 + 512e-9 * users * launches + 68e-9 * users * ins
 
 
-def ondemand_widening(model):
+def ondemand_widening(model, products=3):
     """(widen, eta, delta_s) for nais_pair_bound_topk_widened on the 3-product bound route: widen =
     device float32 [eta', delta_s]; eta' bounds |e3 / e6 - 1| and delta_s bounds |s3 - s6| over
     EVERY (item, candidate) pair of the model, where (e6, s6) are the pair values of the fp16x6
@@ -347,6 +366,13 @@ def ondemand_widening(model):
       theta = (g(6 D + 1) + g(3 D + 1)) (1 + 2^-8) + 2^-23 + 2^-20   both accumulations, both splits,
       eta_a = sum_i |w2_i| (theta Z_i + q + (HP + 4) u 1.01 Z_i)     the w2 . ReLU step is 1-Lipschitz,
       eta'  = eta_a (1 + eta_a) + 2^-20   (two expf calls),  delta_s = theta H2 T2 + q / max Winf.
+    `products=1`: the same for the one-product-logit table (nais_pair_table_bound1_queued), whose
+    logit products are f16(A) f16(B): theta becomes
+      theta_1 = (g(6 D + 1) + g(D + 1)) (1 + 2^-8) + 2^-23 + 2^-10 (1 + 2^-9)
+    (each product within 2^-11 + 2^-11 + 2^-22 of |A||B| for the two f16 roundings, 2^-24 more for
+    the fp32 rounding of A; D + 1 additions), q stands (a hi piece below f16's normal range is off
+    by at most 2^-25 in scaled units, as the hi + lo pair is) and delta_s is the 3-product one: the
+    s tile keeps its three products. DESIGN.md (d), "One product per logit term".
     Cached on the parameters' (data_ptr, version counter), as model._score_params caches its padded
     copies: recomputed (one host sync) only after they change. Here a stale hit is a soundness
     matter, not a stale copy -- bounds that no longer cover the pairs can drop a true winner
@@ -358,9 +384,11 @@ def ondemand_widening(model):
     w1, b1, w2 = model.attn_layer1.weight, model.attn_layer1.bias, model.attn_layer2.weight
     srcs = (eh, et, w1, b1, w2)
     key = tuple((t.data_ptr(), t._version) for t in srcs)
+    if products not in (1, 3):
+        raise ValueError("products: 1 or 3")
     hit = model.__dict__.get("_widen_cache")
-    if hit is not None and hit[0] == key:
-        return hit[1]
+    if hit is not None and hit[0] == key and products in hit[1]:
+        return hit[1][products]
     with torch.no_grad():
         f64 = torch.float64
         D = next((w for w in (8, 16, 32, 64, 128) if w >= w1.shape[1]), w1.shape[1])
@@ -374,7 +402,11 @@ def ondemand_widening(model):
         Z = b1.abs().to(f64) + Winf * H2 * T2
         q = D * 2.0 ** -36 * Winf.max() * Hinf * Tinf
         theta = (g(6 * D + 1) + g(3 * D + 1)) * (1 + 2.0 ** -8) + 2.0 ** -23 + 2.0 ** -20
-        eta_a = (w2.abs().to(f64).reshape(-1) * (theta * Z + q + (HP + 4) * u * 1.01 * Z)).sum()
+        theta_a = theta   # the logit's; delta_s below keeps the 3-product theta
+        if products == 1:
+            theta_a = ((g(6 * D + 1) + g(D + 1)) * (1 + 2.0 ** -8) + 2.0 ** -23
+                       + 2.0 ** -10 * (1 + 2.0 ** -9))
+        eta_a = (w2.abs().to(f64).reshape(-1) * (theta_a * Z + q + (HP + 4) * u * 1.01 * Z)).sum()
         eta = eta_a * (1 + eta_a) + 2.0 ** -20
         ds = theta * H2 * T2 + D * 2.0 ** -36 * Hinf * Tinf
         # the scales are clamped at 2^+-120: operands far outside fp32's middle range void the
@@ -386,8 +418,22 @@ def ondemand_widening(model):
         widen = both.to(torch.float32)
         eta_h, ds_h = (float(v) for v in both.cpu())
     out = (widen, eta_h, ds_h)
-    model.__dict__["_widen_cache"] = (key, out)
+    if hit is None or hit[0] != key:
+        hit = model.__dict__["_widen_cache"] = (key, {})
+    hit[1][products] = out
     return out
+
+
+def ondemand_form(eta1, eta3):
+    """The on-demand route's bound table from the two widenings (ondemand_widening with products 1
+    and 3): 1 = the one-product-logit table when eta'_1 <= PAIR_ONDEMAND_ETA1_MAX (and the knob
+    allows), else 3 = the three-product table when eta'_3 <= PAIR_ONDEMAND_ETA_MAX, else None (the
+    split16 route). Non-finite etas fail both tests."""
+    if PAIR_ONDEMAND_ONE_PRODUCT and np.isfinite(eta1) and eta1 <= PAIR_ONDEMAND_ETA1_MAX:
+        return 1
+    if np.isfinite(eta3) and eta3 <= PAIR_ONDEMAND_ETA_MAX:
+        return 3
+    return None
 
 
 def _ondemand_shape(model, prm):
@@ -417,12 +463,16 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     step in 2 CUs, at the table rate fitted on the queued sweep; without it the 3-product split
     moves in shader-engine steps (a fixed grid), as every call before ABI 16 did.
 
+    `products=1` with `table_queue`: the one-product-logit bound table (ABI 17) as a work queue,
+    at its own fitted rate (X1Q_RATE) in 2-CU steps.
+
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
     split step finer than one CU per shader engine: a fixed-grid launch on a CU count off a
     multiple of 32 leaves an engine short and runs at the next lower multiple."""
     H, din = model.attn_layer1.weight.shape
     prec = getattr(model, "precision", "fp16x6")
+    given = products
     if products is None:   # given: the 3-product bound table under an fp16x6 model
         products = 1 if prec == "fp32" else (6 if prec.startswith("fp16x6") else 3)
     dist = getattr(model, "VARIANT", 0) in (_capi.VARIANT_REGION_DISTANCE, _capi.VARIANT_DISTANCE)
@@ -447,8 +497,14 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     rate = 1.47e15 if x6n else 1.25e15
     if x3q:
         rate = X3Q_RATE
+    # the one-product-logit bound table as a work queue (ABI 17): `products=1` GIVEN with
+    # `table_queue` (products == 1 derived from the model is the exact-fp32 kernel, as ever)
+    x1q = (PAIR_WORK_QUEUE and work_queues and table_queue and given == 1 and gather_bytes == 4
+           and D in (32, 64) and H <= 64 and not prior and not dist)
     din_k = D + (2 if dist else 0)      # the width the kernels multiply (padded)
     t_tab = J * NC * 2.0 * H * din_k * products / (1.3e14 if products == 1 else rate)
+    if x1q:
+        t_tab = J * NC * 2.0 * H * din_k / X1Q_RATE
     if x6n and dist:
         # the distance K-step: 2 v_mfma_f32_16x16x1_4b_f32 (32 cycles each) per PAIR of 16-hidden
         # blocks beside their 2 * 12 * D / 32 f16 MFMAs (16 cycles each): 1 + 16 / (3 D) matrix time
@@ -465,7 +521,7 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
         # profiles/r6/bounded, split_ab), and 4-CU steps: 188 / 68 ran 471.4 ms against 476.9 /
         # 480.2 at 184 / 72 and 490.8 at 180 / 76 on one box (profiles/r6/split_ab)
         per_cu = 66e9
-        if x6n or x3q:
+        if x6n or x3q or x1q:
             # 2-CU steps: config 4 at 190 / 66 ran 476.2 / 476.8 / 478.6 ms against 482.4-482.5 at
             # 188 / 68, interleaved on one box (profiles/r6/split_n1); one rank of N = 2 at 190
             # 239.0 / 239.3 vs 240.5 / 240.9 at 188, N = 4 at 186 even with 184, config 2 at 234
@@ -478,6 +534,8 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
             per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k)
         if x3q:
             per_cu /= X3Q_GATHER_MARGIN
+        if x1q:
+            per_cu /= X1Q_GATHER_MARGIN
     cap = 7.5e12   # the memory side's rate for the gather, chip-wide
     best, best_t = ncu // 2, None
     for n in range((ncu // 4 + step - 1) // step * step, ncu - step + 1, step):
@@ -629,13 +687,18 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
     # the 3-product bound + on-demand refine form of it: decided from the model and the shape alone
     # (every rank of a tau_group decides alike); eta beyond the threshold keeps the split16 form
     ond = None
+    ond_products = 3   # the bound table's f16 products per logit term (ondemand_form)
     if bounded_ok and PAIR_ONDEMAND_REFINE and _ondemand_shape(model, prm):
         widen, eta, ds = ondemand_widening(model)
-        if np.isfinite(eta) and eta <= PAIR_ONDEMAND_ETA_MAX:
-            ond = widen
+        widen1, eta1, _ = ondemand_widening(model, products=1)
+        ond_products = ondemand_form(eta1, eta)
+        if ond_products is not None:
+            ond = widen1 if ond_products == 1 else widen
         if events is not None:
             events.extend((("ondemand_eta", None, None, eta), ("ondemand_delta_s", None, None, ds),
-                           ("ondemand_eta_accepted", None, None, ond is not None)))
+                           ("ondemand_eta_accepted", None, None, ond is not None),
+                           ("ondemand_eta1", None, None, eta1),
+                           ("ondemand_products", None, None, ond_products if ond is not None else 0)))
     if prior is not None:
         pa, pb, alpha, pc = prior
         pri_coords = torch.as_tensor(np.ascontiguousarray(pc, dtype=np.float64)).to(dev)
@@ -662,7 +725,12 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
         return wq_of[h]
 
     def table(tab, c0, w, stream_):
-        if isinstance(tab, tuple) and len(tab) == 1:   # on-demand refine: hi words alone, 3 products
+        if isinstance(tab, tuple) and len(tab) == 1:   # on-demand refine: hi words alone
+            if ond_products == 1:   # one f16 product per logit term (ABI 17)
+                _capi.check(lib.nais_pair_table_bound1_queued(
+                    prm, items.data_ptr(), J, c0, w, _capi.ptr(reg), _capi.ptr(cor), _capi.ptr(llm),
+                    tab[0].data_ptr(), ld, wq(stream_), stream_), "nais_pair_table_bound1_queued")
+                return
             _capi.check(lib.nais_pair_table_bound_queued(
                 prm, items.data_ptr(), J, c0, w, _capi.ptr(reg), _capi.ptr(cor), _capi.ptr(llm),
                 tab[0].data_ptr(), ld, wq(stream_), stream_), "nais_pair_table_bound_queued")
@@ -804,7 +872,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
             table_cus = (auto_table_cus(model, J, NC, entries, ncu, prior is not None,
                                         J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
-                                        users=m, products=3 if ondm[0] else None,
+                                        users=m, products=ond_products if ondm[0] else None,
                                         table_queue=ondm[0])
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
             # the on-demand route runs its streams as queues on the engine grid too: config 4 at

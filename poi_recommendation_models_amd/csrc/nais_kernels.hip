@@ -896,16 +896,20 @@ catalog_score_x3_kernel(DevParams p, const int64_t* __restrict__ indptr,
 // candidate into B fragments that stay in VGPRs for the whole sweep. The per-(c, j) VALU work
 // is then only the epilogue and h_j . t_c -- no per-pair conversions.
 // ---------------------------------------------------------------------------------------------
-template <int DH, int HB, bool DIST, int NW = WAVES, int NPC = 2>
+// NPA: the pieces of A_j the ring holds, NPC everywhere but in the one-product-logit form of the
+// bound table (NPA = 1: the hi piece alone; the kernel's ONE)
+template <int DH, int HB, bool DIST, int NW = WAVES, int NPC = 2, int NPA = NPC>
 struct CfgB {
   static constexpr int D = 2 * DH;
   static constexpr int KS = DH / 8;
   static constexpr int NE = HB * KS * 64;             // uint4 fragment entries per item and piece
-  static constexpr int IB = NE * 16 * NPC;            // bytes per item (all pieces)
+  static constexpr int IB = NE * 16 * NPA;            // bytes per item (all pieces)
   static constexpr int G = IB <= 16384 ? 4 : (IB <= 32768 ? 2 : 1);   // items per ring group
   // LDS chunk rows; fp16x6 keeps 32 (the s tile below) even where 64 would fit (64-row chunks
   // without the s tile: -1..-3 %, profiles/r2/jcb_ab)
-  static constexpr int JCB = (NPC == 3) ? 32 : (2 * G * IB + 64 * D * 4 > 140 * 1024 ? 32 : 64);
+  // (the one-product form keeps the chunks, and with them S_A and the s tile, of its NPA = NPC twin)
+  static constexpr int JCB =
+      (NPC == 3) ? 32 : (2 * G * (IB / NPA * NPC) + 64 * D * 4 > 140 * 1024 ? 32 : 64);
   static constexpr int EPT = (NE + NW * 64 - 1) / (NW * 64);  // build entries per thread
   static constexpr int ADIST = DIST ? HB * 64 : 0;
   static constexpr int EPI = 2 * 2 * HB * 16;
@@ -931,7 +935,12 @@ struct CfgB {
 // NW = waves per workgroup (2 per SIMD at 8). D, H <= 64 pipeline the epilogue (CfgB::PIPE).
 // QUEUE: the work-queue form of pair-table mode (tab.work given); false compiles the work loop away,
 // so per-user mode and the fixed-grid tables keep the code they had before the queue existed.
-template <int DH, int HB, int VAR, int NW, int NPC, bool QUEUE = false>
+// ONE: the one-product-logit form of the bound table (nais_pair_table_bound1_queued): the ring
+// holds the hi piece of A_j alone and the logit loop issues hi*hi only, an attention logit good to
+// ~2^-10 of its terms instead of 2^-21; the s tile keeps its NPC pieces and products, so s has the
+// bits of the ONE = false instance. Scales, accumulator start, epilogue, tail and work loop are
+// shared. false compiles it away, as QUEUE.
+template <int DH, int HB, int VAR, int NW, int NPC, bool QUEUE = false, bool ONE = false>
 __global__ void __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW)   // >= 2 waves per SIMD per CU
 catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
                          const int64_t* __restrict__ indices, const int32_t* __restrict__ users,
@@ -940,16 +949,19 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
                          int64_t score_ld, int32_t* __restrict__ nan_count, TableOut tab) {
   constexpr bool REGION = VarT<VAR>::REGION;
   constexpr bool DIST = VarT<VAR>::DIST;
-  using C = CfgB<DH, HB, DIST, NW, NPC>;
+  constexpr int NPA = ONE ? 1 : NPC;   // pieces of A_j in the ring = products per logit K-step
+  using C = CfgB<DH, HB, DIST, NW, NPC, NPA>;
   constexpr int D = C::D, KS = C::KS, NE = C::NE, G = C::G, JCB = C::JCB, EPT = C::EPT;
   constexpr int THREADS = NW * 64, CAND_PER_BLOCK = NW * 32;   // shadow the 8-wave defaults
   constexpr bool PIPE = C::PIPE;
+  static_assert(!ONE || (NPC == 2 && PIPE && !DIST),
+                "one-product logits: the pipelined fp16x3 shapes, no distance inputs");
   // s = h_j . t_c for the chunk's 32 items on the matrix pipe (one 32x32 tile per wave and chunk,
   // the same split-fp16 3-product scheme) instead of a 2*DH-term VALU dot per item and lane
   constexpr bool SMF = JCB == 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);       // [2 groups][G items][piece][NE]
-  float* Adist = reinterpret_cast<float*>(ring + 2 * G * NPC * NE);
+  float* Adist = reinterpret_cast<float*>(ring + 2 * G * NPA * NE);
   float* Eimg = Adist + C::ADIST;
   float* Escl = Eimg + C::EPI;          // WLDS: per wave [S*b1 | w2/S] (EPI floats each)
   float* red = Escl + C::ESCL;
@@ -1093,7 +1105,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   // build the fragments of chunk-local item jj into ring slot (grp, it); wv is pre-scaled by S_A
   auto build = [&](int jj, int grp, int it) {
     const float* hr = hrows + jj * D;
-    uint4* dst = ring + ((grp * G + it) * NPC) * NE;
+    uint4* dst = ring + ((grp * G + it) * NPA) * NE;
 #pragma unroll
     for (int q = 0; q < EPT; ++q) {
       const int e = tid + q * THREADS;
@@ -1111,10 +1123,17 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
         a[5] = wv[q][5] * h1.y;
         a[6] = wv[q][6] * h1.z;
         a[7] = wv[q][7] * h1.w;
-        half8 pc[NPC];
-        split_pieces<NPC>(a, pc);
+        if constexpr (ONE) {   // the hi piece alone: f16(a), RNE
+          half8 hi;
 #pragma unroll
-        for (int q2 = 0; q2 < NPC; ++q2) dst[q2 * NE + e] = *reinterpret_cast<const uint4*>(&pc[q2]);
+          for (int x = 0; x < 8; ++x) hi[x] = (_Float16)a[x];
+          dst[e] = *reinterpret_cast<const uint4*>(&hi);
+        } else {
+          half8 pc[NPC];
+          split_pieces<NPC>(a, pc);
+#pragma unroll
+          for (int q2 = 0; q2 < NPC; ++q2) dst[q2 * NE + e] = *reinterpret_cast<const uint4*>(&pc[q2]);
+        }
       }
     }
   };
@@ -1178,13 +1197,14 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
       if (MMA) {
 #pragma unroll
         for (int hb = 0; hb < HB; ++hb) {
-          half8 ap_[NPC];
+          half8 ap_[NPA];
 #pragma unroll
-          for (int q = 0; q < NPC; ++q) {
+          for (int q = 0; q < NPA; ++q) {
             const uint4 u4 = src[q * NE + (hb * KS + s) * 64 + lane];
             ap_[q] = *reinterpret_cast<const half8*>(&u4);
           }
-          accN[hb] = mfma_pieces<NPC>(ap_, tb[s], accN[hb]);
+          if constexpr (ONE) accN[hb] = mfma16(ap_[0], tb[s][0], accN[hb]);
+          else accN[hb] = mfma_pieces<NPC>(ap_, tb[s], accN[hb]);
         }
       }
       if constexpr (EPIL) {
@@ -1235,13 +1255,14 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
       for (int s = 0; s < KS; ++s) {
 #pragma unroll
         for (int hb = 0; hb < HS; ++hb) {
-          half8 ap_[NPC];
+          half8 ap_[NPA];
 #pragma unroll
-          for (int q = 0; q < NPC; ++q) {
+          for (int q = 0; q < NPA; ++q) {
             const uint4 u4 = src[q * NE + ((h0 + hb) * KS + s) * 64 + lane];
             ap_[q] = *reinterpret_cast<const half8*>(&u4);
           }
-          acc[hb] = mfma_pieces<NPC>(ap_, tb[s], acc[hb]);
+          if constexpr (ONE) acc[hb] = mfma16(ap_[0], tb[s][0], acc[hb]);
+          else acc[hb] = mfma_pieces<NPC>(ap_, tb[s], acc[hb]);
         }
       }
 #pragma unroll
@@ -1345,7 +1366,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
       for (int it = 0; it < G; ++it) {
         const int jj = g * G + it;
         if (jj < jn) {
-          const uint4* src = ring + (((g & 1) * G + it) * NPC) * NE;
+          const uint4* src = ring + (((g & 1) * G + it) * NPA) * NE;
           if constexpr (PIPE) {   // item jj into acc2[jj & 1] (G even: static), item jj - 1 from the other
             step(std::true_type{}, std::true_type{}, src, acc2[it & 1], acc2[(it + 1) & 1], jj, prev,
                  prev >= 0);
@@ -2897,6 +2918,43 @@ int launch_catalog_x3b(const DevParams& d, const int64_t* indptr, const int64_t*
   }
 }
 
+// The one-product-logit bound table (catalog_score_x3b_kernel<..., ONE = true>): pair-table mode of
+// NAIS_basic at padded D in {32, 64}, H <= 64 -- the shapes the on-demand refine covers -- as a
+// work queue with tab.work, on the fixed grid without.
+template <int DH, int HB>
+int launch_x3b_one(const DevParams& d, const int64_t* indices, int ng, hipStream_t stream,
+                   const TableOut& tab) {
+  constexpr int NW = WAVES, VAR = NAIS_VARIANT_BASIC;
+  const size_t lds = CfgB<DH, HB, false, NW, 2, 1>::BYTES;
+  auto kern = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, false, true>;
+  auto kq = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, true, true>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kq),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  dim3 grid = table_grid(tab, ng, NW * 32);
+  TableOut t = tab;
+  if (t.work) {   // as launch_catalog_x3b: one workgroup per CU of the stream's mask
+    t.ngroups = (int32_t)grid.y;
+    t.ntiles = (int32_t)grid.x;
+    const int ncu = nais_internal_stream_cus(stream);
+    if (ncu <= 0) return fail(NAIS_E_HIP, "device attributes");
+    grid = dim3((unsigned)std::min<int64_t>((int64_t)grid.x * grid.y, ncu), 1, 1);
+    if (hipMemsetAsync(t.work, 0, sizeof(int32_t), stream) != hipSuccess)
+      return fail(NAIS_E_HIP, "hipMemsetAsync(work)");
+    hipLaunchKernelGGL(kq, grid, dim3(NW * 64), lds, stream, d, nullptr, indices, nullptr, nullptr,
+                       nullptr, nullptr, nullptr, 0, nullptr, t);
+    return check_launch("catalog_score_x3b_kernel (one product, queue)");
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, stream, d, nullptr, indices, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, 0, nullptr, t);
+  return check_launch("catalog_score_x3b_kernel (one product)");
+}
+
 template <int DH, int HB, int VAR>
 int launch_catalog_x6b(const DevParams& d, const int64_t* indptr, const int64_t* indices,
                        const int32_t* users, int nb, const int64_t* region_of, const double* coords,
@@ -3129,9 +3187,10 @@ namespace {
 int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64_t num_items,
                         int64_t col0, int64_t cols, const int64_t* region_of, const double* coords,
                         const double* latlon_mat, float* e, float* es, int64_t ld, int32_t* work,
-                        void* stream, bool split = false, bool bound = false) {
+                        void* stream, bool split = false, bool bound = false, bool one = false) {
   // bound: the hi words of the split16 form alone, from the 3-product (fp16x3) kernels whatever
   // params->precision says -- es stays null and no (e, e*s) pair is stored (nais_pair_table_bound)
+  // one (with bound): from the one-product-logit form of that kernel (nais_pair_table_bound1_queued)
   Shape sh;
   int rc = validate(params, &sh);
   if (rc) return rc;
@@ -3152,6 +3211,9 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
   if (rc) return rc;
   if (bound && (sh.gen_tab || sh.HB > 4))
     return fail(NAIS_E_UNSUPPORTED, "nais_pair_table_bound: native embed widths with hidden <= 128 only");
+  if (one && (params->variant != NAIS_VARIANT_BASIC || (sh.DH != 16 && sh.DH != 32) || sh.HB > 2))
+    return fail(NAIS_E_UNSUPPORTED,
+                "nais_pair_table_bound1_queued: NAIS_basic, embed_dim 32 or 64, hidden <= 64");
   if (sh.gen_tab)
     return nais_gx_catalog(params, nullptr, nullptr, nullptr, 0, items, num_items, col0, cols,
                            region_of, coords, latlon_mat, nullptr, 0, nullptr, e, es, ld, st, split);
@@ -3171,7 +3233,12 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
     tab.es = es ? es + base * ld * (split ? 2 : 1) : nullptr;
     tab.col0 = col0;
     const int ng = (int)((tab.nitems + tab.gi - 1) / tab.gi);
-    if (precision == NAIS_PRECISION_FP32)
+    if (one)
+      rc = sh.DH == 16 ? (sh.HB == 1 ? launch_x3b_one<16, 1>(d, items + base, ng, st, tab)
+                                     : launch_x3b_one<16, 2>(d, items + base, ng, st, tab))
+                       : (sh.HB == 1 ? launch_x3b_one<32, 1>(d, items + base, ng, st, tab)
+                                     : launch_x3b_one<32, 2>(d, items + base, ng, st, tab));
+    else if (precision == NAIS_PRECISION_FP32)
       NAIS_DISPATCH(launch_catalog, sh.DH, sh.HB, params->variant, d, nullptr, items + base, nullptr,
                     ng, region_of, coords, latlon_mat, nullptr, 0, nullptr, st, tab);
     else if (precision == NAIS_PRECISION_FP16X6 || precision == NAIS_PRECISION_FP16X6_PAIRSPLIT)
@@ -3218,6 +3285,15 @@ int32_t nais_pair_table_bound_queued(const nais_params_t* params, const int64_t*
                                      int32_t* work, void* stream) {
   return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
                          reinterpret_cast<float*>(hi), nullptr, ld, work, stream, false, true);
+}
+
+int32_t nais_pair_table_bound1_queued(const nais_params_t* params, const int64_t* items,
+                                      int64_t num_items, int64_t col0, int64_t cols,
+                                      const int64_t* region_of, const double* coords,
+                                      const double* latlon_mat, uint32_t* hi, int64_t ld,
+                                      int32_t* work, void* stream) {
+  return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
+                         reinterpret_cast<float*>(hi), nullptr, ld, work, stream, false, true, true);
 }
 
 int32_t nais_pair_scales(const nais_params_t* params, const int64_t* items, int64_t num_items,
