@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 17   /* 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 18   /* 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -569,6 +569,64 @@ int32_t nais_disent_forward(const nais_disent_params_t* params, const int64_t* h
                             void* stream);
 int32_t nais_pair_distances(const double* coords, const int64_t* hist, int64_t n,
                             const int64_t* target, int64_t b, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * GeoIE (model.py:757-828; DESIGN.md (c) "GeoIE"): for user u with CSR-order history hist[0..h)
+ * and candidate c,
+ *   Gr[e][j] = flat[e*h + j], flat = the rows GeoInfluence[hist[0..h)] laid end to end (h*D floats):
+ *              the reference's reshape([b, -1, h]) of a [b, h, D] gather (model.py:795-798), not a
+ *              transpose
+ *   S[j]     = sum_e Gr[e][j] * GeoSusceptibility[c][e]                      (model.py:800-802)
+ *   f[j]     = a * d_j ** b,  d_j = float32(min(max(0.01, dist(coo_c, coo_hist[j])), 100))
+ *              (run.py:40-46 builds the float64 matrix, batches.py:256-267 slices and casts it)
+ *   out      = sigmoid(UserPreference[u] . PoiPreference[c] + (sum_j S[j] f[j]) / h)
+ * in fp32; a and b are the module's Python floats, used as float32 (torch's scalar operands).
+ *
+ *   nais_geoie_table    f[r*ld + c-col0] = a * d ** b for item rows r < num_items (items[] and the
+ *                       rowmap of nais_pair_rows) and candidates c in [col0, col0 + cols): the
+ *                       model's only (history POI, candidate) term, evaluated once per pair of a
+ *                       user list instead of once per (user, history entry, candidate). Exactly
+ *                       one distance source: coords [P, 2] float64 (lat, lng) -- powerLaw.dist in
+ *                       float64 on the device, clamped to [0.01, 100], then cast -- or dist_mat
+ *                       [P, P] float64, the caller's run.distance_mat result, read at [c][item]
+ *                       and cast (run.py:683, batches.py:256). ld >= cols.
+ *   nais_geoie_score    scores[slot*score_ld + c - score_col0] = out for users[slot] and every c in
+ *                       [col0, col0 + cols); history POIs are written as -1 (they are not
+ *                       candidates, batches.py:250), NaN scores counted into *nan_count (may be
+ *                       NULL). Replaces get_GeoIE_batch_test + the forward of
+ *                       validation.py:187-189; nais_topk_rows then is validation.py:190. S is an
+ *                       exact-fp32 MFMA product per (32 history entries, 32 candidates) tile, the
+ *                       history staged in LDS chunks (any h), any embed_dim 1..256. Every listed
+ *                       user's history POIs must be rows of the table (rowmap, num_items).
+ *   nais_geoie_forward  out[i] for rows (user[i], target[i], hist[i*hist_ld + 0..n),
+ *                       distances[i*dist_ld + 0..n) float32): the tensors GeoIE.forward receives
+ *                       (model.py:785), evaluated with the arithmetic and summation order of
+ *                       nais_geoie_score, so a catalog winner re-scored here has the same bits.
+ * num_pois < 2^24 (NAIS_E_UNSUPPORTED above).
+ */
+typedef struct nais_geoie_params {
+  int32_t embed_dim;            /* D, 1..256                                                  */
+  int64_t num_users;            /* rows of user_pref                                          */
+  int64_t num_pois;             /* P = rows of the three POI tables                           */
+  float a, b;                   /* the power law f = a * d ** b (model.py:763-764, :799)      */
+  const float* user_pref;       /* UserPreference.weight    [num_users, D]  model.py:769      */
+  const float* poi_pref;        /* PoiPreference.weight     [P, D]          model.py:770      */
+  const float* geo_influence;   /* GeoInfluence.weight      [P, D]          model.py:771      */
+  const float* geo_suscept;     /* GeoSusceptibility.weight [P, D]          model.py:772      */
+} nais_geoie_params_t;
+
+int32_t nais_geoie_table(const double* coords, const double* dist_mat, int64_t num_pois,
+                         const int64_t* items, int64_t num_items, int64_t col0, int64_t cols,
+                         float a, float b, float* f, int64_t ld, void* stream);
+int32_t nais_geoie_score(const nais_geoie_params_t* params, const int64_t* indptr,
+                         const int64_t* indices, const int32_t* users, int32_t num_users,
+                         const int32_t* rowmap, const float* f, int64_t ld, int64_t num_items,
+                         int64_t col0, int64_t cols, float* scores, int64_t score_ld,
+                         int64_t score_col0, int32_t* nan_count, void* stream);
+int32_t nais_geoie_forward(const nais_geoie_params_t* params, const int64_t* user,
+                           const int64_t* target, const int64_t* hist, int64_t b, int64_t n,
+                           int64_t hist_ld, const float* distances, int64_t dist_ld, float* out,
+                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step of NAIS_basic on one get_NAIS_batch batch (batches.py:24-50):

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -35,7 +35,15 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_topk_merge_f64", "nais_train_ucache_size", "nais_pair_table_split",
            "nais_pair_bound_topk", "nais_pair_refine_topk", "nais_pair_table_bound",
            "nais_pair_bound_topk_widened", "nais_pair_scales", "nais_pair_refine_topk_exact",
-           "nais_pair_recompute", "nais_pair_table_bound_queued", "nais_pair_table_bound1_queued")
+           "nais_pair_recompute", "nais_pair_table_bound_queued", "nais_pair_table_bound1_queued",
+           "nais_geoie_table", "nais_geoie_score", "nais_geoie_forward")
+
+
+class NaisGeoIEParams(ctypes.Structure):
+    """Mirror of `nais_geoie_params_t` (include/nais.h)."""
+    _fields_ = [("embed_dim", ctypes.c_int32), ("num_users", ctypes.c_int64),
+                ("num_pois", ctypes.c_int64), ("a", ctypes.c_float), ("b", ctypes.c_float)] + \
+        [(n, ctypes.c_void_p) for n in ("user_pref", "poi_pref", "geo_influence", "geo_suscept")]
 
 
 class NaisDotTables(ctypes.Structure):
@@ -255,6 +263,14 @@ def load(path: str | None = None):
     lib.nais_pair_recompute.restype = i32
     lib.nais_pair_recompute.argtypes = [ctypes.POINTER(NaisParams), vp, i64, vp, vp, i64, i64, vp, i64,
                                         vp, i64, vp, vp, vp]
+    lib.nais_geoie_table.restype = i32
+    lib.nais_geoie_table.argtypes = [vp, vp, i64, vp, i64, i64, i64, f32, f32, vp, i64, vp]
+    lib.nais_geoie_score.restype = i32
+    lib.nais_geoie_score.argtypes = [ctypes.POINTER(NaisGeoIEParams), vp, vp, vp, i32, vp, vp, i64,
+                                     i64, i64, i64, vp, i64, i64, vp, vp]
+    lib.nais_geoie_forward.restype = i32
+    lib.nais_geoie_forward.argtypes = [ctypes.POINTER(NaisGeoIEParams), vp, vp, vp, i64, i64, i64, vp,
+                                       i64, vp, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

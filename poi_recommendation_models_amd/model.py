@@ -984,3 +984,114 @@ class transform_attn(_NearPOIModel):
         _capi.check(_capi.load().nais_dot_single_fixup(
             self.dot_tables(), csr.indptr.data_ptr(), csr.indices.data_ptr(), users.data_ptr(), m, c0,
             c1 - c0, scores.data_ptr(), c1 - c0, c0, stream), "nais_dot_single_fixup")
+
+
+class GeoIE(nn.Module):
+    """GeoIE (model.py:757-828): `GeoIE(user_count, POI_count, emb_dimension, neg_num, a, b)`,
+    the reference's attribute and state_dict names, Xavier-normal init.
+
+    With grad disabled (`torch.no_grad()`, as run.py:720-723 evaluates) the forward is the HIP
+    kernel `nais_geoie_forward`; with grad enabled it is the reference's own sequence of torch ops
+    on the device, so `train_GeoIE`'s loop (run.py:702-715: forward, `loss_function`, `backward()`,
+    SGD step) runs unchanged. A fused training step is not built. Off the ROCm device it raises."""
+
+    def __init__(self, user_count, POI_count, emb_dimension, neg_num, a, b):
+        super().__init__()
+        self.emb_dimension = emb_dimension
+        self.scaling = 10
+        self.negnum = neg_num
+        self.a = a
+        self.b = b
+        self.UserPreference = nn.Embedding(user_count, emb_dimension)
+        self.PoiPreference = nn.Embedding(POI_count, emb_dimension)
+        self.GeoInfluence = nn.Embedding(POI_count, emb_dimension)
+        self.GeoSusceptibility = nn.Embedding(POI_count, emb_dimension)
+        self.init_emb()
+        self.POI_count = POI_count
+        self.sigmoid = nn.Sigmoid()
+        self.loss_func = nn.BCELoss()
+        self._last_nan = None
+
+    def init_emb(self):                                        # model.py:779-783
+        nn.init.xavier_normal_(self.UserPreference.weight)
+        nn.init.xavier_normal_(self.PoiPreference.weight)
+        nn.init.xavier_normal_(self.GeoInfluence.weight)
+        nn.init.xavier_normal_(self.GeoSusceptibility.weight)
+
+    def _check_device(self, *tensors):
+        dev = self.UserPreference.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"GeoIE: the model runs only on a ROCm device (parameters are on {dev}); "
+                               "move it with .to('cuda')")
+        for t in tensors:
+            if t is not None and t.device != dev:
+                raise RuntimeError(f"GeoIE: input on {t.device}, parameters on {dev}")
+        for n, p in self.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"GeoIE: parameter {n} must be contiguous float32")
+        return dev
+
+    def geoie_params(self) -> _capi.NaisGeoIEParams:
+        """`nais_geoie_params_t` view of this module's parameters (device pointers, no copies)."""
+        q = _capi.NaisGeoIEParams()
+        q.embed_dim = int(self.emb_dimension)
+        q.num_users = int(self.UserPreference.weight.shape[0])
+        q.num_pois = int(self.PoiPreference.weight.shape[0])
+        q.a, q.b = float(self.a), float(self.b)
+        q.user_pref = self.UserPreference.weight.data_ptr()
+        q.poi_pref = self.PoiPreference.weight.data_ptr()
+        q.geo_influence = self.GeoInfluence.weight.data_ptr()
+        q.geo_suscept = self.GeoSusceptibility.weight.data_ptr()
+        return q
+
+    def forward(self, user_id, targets, history, check_in_num, distances):   # model.py:785-813
+        dev = self._check_device(user_id, targets, history, check_in_num, distances)
+        if history.dim() != 2 or distances.shape != history.shape or \
+                targets.shape[0] != history.shape[0] or user_id.shape[0] != history.shape[0]:
+            raise ValueError(f"history and distances must be [b, h], user_id and targets [b]; got "
+                             f"{tuple(history.shape)}, {tuple(distances.shape)}, "
+                             f"{tuple(user_id.shape)}, {tuple(targets.shape)}")
+        batch_size, history_size = history.shape
+        if history_size == 0:   # the reference's reshape raises here (model.py:798)
+            who = ", ".join(str(u) for u in sorted(set(user_id.reshape(-1).tolist())))
+            raise ValueError(f"GeoIE: empty history (user {who})")
+        wuj = 1 + torch.log(1 + check_in_num * (10 ** self.scaling))          # model.py:812
+        if torch.is_grad_enabled():
+            UPre = self.UserPreference(user_id)
+            PPre = self.PoiPreference(targets)
+            hj = self.GeoSusceptibility(targets)
+            g = self.GeoInfluence(history).reshape([batch_size, -1, history_size])
+            fij = self.a * (distances ** self.b)
+            hj = torch.reshape(hj, [batch_size, -1, 1])
+            t2 = torch.sum(g * hj, dim=1) * fij
+            yij = torch.sum(t2, dim=-1) / history_size
+            UPre = torch.reshape(UPre, [batch_size, 1, -1])
+            PPre = torch.reshape(PPre, [batch_size, -1, 1])
+            tz = torch.bmm(UPre, PPre).squeeze(-1)
+            return self.sigmoid(tz + yij.unsqueeze(1)), wuj
+        user_id = user_id.reshape(-1).to(torch.int64).contiguous()
+        targets = targets.reshape(-1).to(torch.int64).contiguous()
+        history = history.to(torch.int64)
+        if history.stride(1) != 1:
+            history = history.contiguous()
+        distances = distances.to(torch.float32)
+        if distances.stride(1) != 1:
+            distances = distances.contiguous()
+        out = torch.empty(batch_size, 1, dtype=torch.float32, device=dev)
+        _capi.check(_capi.load().nais_geoie_forward(
+            self.geoie_params(), user_id.data_ptr(), targets.data_ptr(), history.data_ptr(), batch_size,
+            history_size, history.stride(0), distances.data_ptr(), distances.stride(0), out.data_ptr(),
+            _capi.stream_handle(dev)), "nais_geoie_forward")
+        return out, wuj
+
+    def loss_function(self, prediction, label, weight):       # model.py:816-828
+        t1 = label * (torch.log(prediction + 1e-10))
+        t2 = (1 - label) * (torch.log(1 - prediction + 1e-10))
+        loss = torch.sum(-weight * (t1 + t2))
+        if torch.isnan(loss).item():
+            print(prediction)
+            print(label)
+            print(weight)
+            print(t1)
+            print(t2)
+        return torch.sum(loss)

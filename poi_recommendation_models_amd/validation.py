@@ -120,6 +120,22 @@ def NAIS_region_distance_validation(model, args, num_users, test_positive, val_p
     return _metrics(test_positive, val_positive, rec, k_list)
 
 
+def GeoIE_validation(model, args, num_users, test_positive, val_positive, train_matrix, k_list,
+                     dist_mat, poi_coords=None):
+    """validation.py:183-195 (GeoIE). The reference slices a P x P float64 `dist_mat`
+    (run.py:40-46, :683) per candidate in a Python loop (batches.py:254-258). Pass `poi_coords`
+    ([P, 2] lat/lng, the coordinates dist_mat was built from) to have the device form the same
+    clamped float64 distances on the fly instead -- nothing P x P is then allocated, and
+    `dist_mat=None` is allowed. A `dist_mat` given (numpy or tensor) is uploaded once and read by
+    the table kernel. A user with an empty history raises ValueError (the reference's reshape
+    raises, model.py:798). Single-process only: there is no distributed GeoIE evaluation."""
+    from .geoie import score_topk as geoie_topk
+    model.eval()                                               # validation.py:184
+    ids, _ = geoie_topk(model, train_matrix, range(num_users), args.topk,
+                        dist_mat=None if poi_coords is not None else dist_mat, coords=poi_coords)
+    return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
+
+
 def new4_validation(model, args, num_users, test_positive, val_positive, train_matrix,
                     businessRegionEmbedList, k_list, nearPOI, distributed=None):
     """validation.py:254-280 (New4): the context tables are built once (the reference rebuilds
