@@ -142,7 +142,8 @@ class _NAISDevice(nn.Module):
         variants' [E | region] rows), attn_layer1's columns placed at the padded positions, the
         distance columns after them. Exact: a padded dimension contributes 0 * x = 0 to W1 x and
         to h . t, and the per-wave power-of-two scales see the same maxima. The copies are rebuilt
-        when a parameter changes (tensor version counter). Training reads the parameters as they
+        when a parameter changes (tensor version counter) and when a New4-family model rebuilds
+        its extended tables (extended_tables drops them). Training reads the parameters as they
         are (the training kernels take any D, H <= 128)."""
         D = int(self.embed_size)
         if D in NATIVE_WIDTHS or D > NATIVE_WIDTHS[-1]:
@@ -753,6 +754,10 @@ class _NearPOIModel(_NAISDevice):
         xt = torch.empty(P, D, device=dev)
         self._build_tables(near, xh, xt)
         self._ext = (key, (xh, xt), near)
+        # _score_params' padded copies are keyed on (data_ptr, version) of the tables. These are
+        # fresh blocks filled by raw kernels -- version 0 every time, and the caching allocator
+        # hands a later build the blocks of an earlier one -- so the copies go with the build.
+        self.__dict__.pop("_pad_cache", None)
         return xh, xt
 
     def _item_tables(self):

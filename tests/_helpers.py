@@ -21,6 +21,12 @@ def params_from(z, tag):
             and ("." in k[len(pre):])}
 
 
+def family_wide_params(z, cfg, member):
+    """Parameters of one member of new4_family_wide.npz (stored as float16, which holds them
+    exactly: make_golden_new4_family_wide.py) widened to the float32 the reference computed with."""
+    return {k: v.astype(np.float32) for k, v in params_from(z, f"{cfg}/{member}").items()}
+
+
 def positives_from(z, kind):
     flat, lens = z[kind + "_flat"], z[kind + "_len"]
     out, o = [], 0

@@ -200,9 +200,10 @@ def test_disentangled_forward_golden(tag, n):
     assert int(m._last_nan.item()) == int(np.isnan(ref).sum())
 
 
-@pytest.mark.parametrize("D,H", [(16, 8), (64, 64), (128, 100)])
+@pytest.mark.parametrize("D,H", [(16, 8), (64, 64), (128, 100), (1, 1), (100, 65), (127, 127)])
 def test_disentangled_shapes_vs_oracle(D, H):
-    """Per-row histories, D / H up to 128 (two hidden units per lane), a strided history view."""
+    """Per-row histories, D / H up to 128 (two hidden units per lane), a strided history view;
+    odd widths, and a second hidden unit on one lane only (H = 65) or on all but one (H = 127)."""
     rng = np.random.default_rng(D + H)
     P, R, b, n = 300, 12, 33, 17
     f = np.float32

@@ -7,7 +7,8 @@ import math
 import numpy as np
 import pytest
 
-from _helpers import (assert_topk_equivalent, load_golden, params_from, positives_from)
+from _helpers import (assert_topk_equivalent, family_wide_params, load_golden, params_from,
+                      positives_from)
 from oracle import metrics_oracle, nais_oracle, powerlaw_oracle
 
 # fp32 CPU restatement vs the reference's torch CPU kernels: different GEMM summation orders
@@ -198,6 +199,25 @@ def test_forward_new4_family(member, n):
     hist, tgt, ref = (z[f"{member}/n{n}/{k}"] for k in ("hist", "target", "pred"))
     got = nais_oracle.forward_family(member, p, z["near"], 32, hist, tgt)
     assert np.array_equal(np.isnan(got), np.isnan(ref))
+    ok = ~np.isnan(ref)
+    np.testing.assert_allclose(got[ok], ref[ok], rtol=0, atol=ORACLE_ATOL)
+
+
+@pytest.mark.parametrize("member", ("New4",) + FAMILY)
+@pytest.mark.parametrize("cfg", ["wide", "odd"])
+@pytest.mark.parametrize("n", [1, 9])
+def test_forward_new4_family_wide(member, cfg, n):
+    """All eight table-based members at the reference driver's widths (embed_size = hidden = 128,
+    50 near POIs) and at an embed_size off the native widths (48 / 40 / 7), run by the reference
+    (tests/golden/make_golden_new4_family_wide.py): pins the oracle at the shapes
+    test_gpu_family_shapes.py leans on it for."""
+    z = load_golden("new4_family_wide.npz")
+    E = int(z[f"{cfg}/shape"][1])
+    p = family_wide_params(z, cfg, member)
+    hist, tgt, ref = (z[f"{cfg}/{member}/n{n}/{k}"] for k in ("hist", "target", "pred"))
+    got = nais_oracle.forward_family(member, p, z[f"{cfg}/near"], E, hist, tgt)
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+    assert np.isnan(ref[0]) == (n == 1)       # the one-item history that is its own target: 0/0
     ok = ~np.isnan(ref)
     np.testing.assert_allclose(got[ok], ref[ok], rtol=0, atol=ORACLE_ATOL)
 
