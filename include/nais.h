@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 18   /* 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 19   /* 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -627,6 +627,77 @@ int32_t nais_geoie_forward(const nais_geoie_params_t* params, const int64_t* use
                            const int64_t* target, const int64_t* hist, int64_t b, int64_t n,
                            int64_t hist_ld, const float* distances, int64_t dist_ld, float* out,
                            void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * GeoIE training (run.py:687-715, model.py:785-828, batches.py:204-242; DESIGN.md "GeoIE training").
+ * One batch is one user u: hist[h] = the user's positives in shuffled order, b = h * (1 + num_ng)
+ * rows target[b] = [pos_i, neg_i1 .. neg_i,num_ng], labels 1 / 0, freq[b] int64, distances[b, h]
+ * float32 = dist_mat[target_i][hist_j]. With the symbols of the GeoIE block above, c_i = target[i]:
+ *   p_i   = sigmoid(UserPreference[u] . PoiPreference[c_i] + (sum_j S_i[j] f_ij) / h)
+ *   w_i   = 1 + log(float32(1 + freq_i * 10^10))                             (model.py:812)
+ *   L     = sum_i -w_i (label_i log(p_i + 1e-10) + (1 - label_i) log(1 - p_i + 1e-10))   (:816-828)
+ *   d_i   = -w_i (label_i / (p_i + 1e-10) - (1 - label_i) / (1 - p_i + 1e-10)) p_i (1 - p_i)
+ *           -- the composed form autograd produces, NOT w (p - label): where p_i rounds to exactly
+ *           0 or 1 the reference's gradient is 0
+ *   dUserPreference[u]        = sum_i d_i PoiPreference[c_i]
+ *   dPoiPreference[c_i]       = d_i UserPreference[u]
+ *   dGeoSusceptibility[c_i][e] = (d_i / h) sum_j Gr[e][j] f_ij
+ *   dflat[e*h + j]            = sum_i (d_i / h) f_ij GeoSusceptibility[c_i][e], which is the
+ *                               gradient of GeoInfluence[hist[(e*h+j) / D]][(e*h+j) % D]
+ *   torch.optim.SGD (run.py:687, no momentum): g' = g + weight_decay p; p -= lr g'. With
+ *   weight_decay == 0 only the touched rows change (1 user row, the b target rows of PoiPreference
+ *   and GeoSusceptibility, the h history rows of GeoInfluence), every other row stays bit-identical;
+ *   otherwise every element of the four tables moves, the untouched rows by one dense pass.
+ *
+ *   nais_geoie_make_train_batch  get_GeoIE_batch (batches.py:204-242) on the device. hist / target /
+ *       labels as nais_make_train_batch (same negative distribution; h * (1 + num_ng) <= num_pois),
+ *       freq[i] = int64(data[indptr[user] + i / (1 + num_ng)]) -- attached by CSR POSITION while
+ *       the positives are shuffled, as batches.py:238-239 -- and distances[i*dist_ld + j] from
+ *       exactly one source, as nais_geoie_table derives them: coords [P, 2] float64 (powerLaw.dist
+ *       in float64, clamped to [0.01, 100], cast) or dist_mat [P, P] float64 read at
+ *       [target][hist] and cast. data = the CSR values as float64. *err is set to 1 if h disagrees
+ *       with indptr.
+ *   nais_geoie_train_step  replaces run.py:705-715 for one batch: forward, loss_function,
+ *       backward and the SGD step, in place on the four tables of `params` (written through for
+ *       this call). *loss_sum += L; *bad_rows += rows whose loss term is not finite (the update
+ *       still goes through: the reference only prints, model.py:820-826); pred[b] (optional) = p.
+ *       grads (optional, any member NULL): the row gradients, in batch order. stamp_target /
+ *       stamp_hist: [P] int32 each, zero-initialised once, `tag` a value not used by an earlier
+ *       step (the caller's step counter, as nais_adagrad_state_t's stamps): they mark the rows the
+ *       step touches, and detect a repeated target or history entry or an id outside [0, P),
+ *       which sets *err (1 repeat, 2 range). While *err is non-zero NO table is written -- a
+ *       repeat is never applied half-summed -- so the caller checks and clears it. Any embed_dim
+ *       1..256, h >= 1, b >= 1 (b need not be h * (1 + num_ng)). Exact-fp32 MFMA products; the
+ *       summation order differs from nais_geoie_forward's, so pred agrees with it to rounding,
+ *       not bitwise.
+ *   nais_sgd  the dense pass: p -= lr (g + weight_decay p) for every row of a [rows, dim] tensor
+ *       whose stamp is not `tag` (stamp may be NULL) and that is not skip_row (-1: none); grad may
+ *       be NULL (zero). Nothing is written while *err (optional) is non-zero.
+ */
+typedef struct nais_geoie_train_grads {
+  float* user_pref;             /* [D]     dUserPreference[u]                                  */
+  float* poi_pref;              /* [b, D]  dPoiPreference[target[i]]                           */
+  float* geo_suscept;           /* [b, D]  dGeoSusceptibility[target[i]]                       */
+  float* geo_influence;         /* [h, D]  dGeoInfluence[hist[r]]                              */
+} nais_geoie_train_grads_t;
+
+int32_t nais_geoie_make_train_batch(const int64_t* indptr, const int64_t* indices,
+                                    const double* data, int64_t user, int64_t h, int64_t num_pois,
+                                    int32_t num_ng, uint64_t seed, const double* coords,
+                                    const double* dist_mat, int64_t* hist, int64_t* target,
+                                    float* labels, int64_t* freq, float* distances, int64_t dist_ld,
+                                    int32_t* err, void* stream);
+size_t nais_geoie_train_step_workspace_size(const nais_geoie_params_t* params, int64_t b, int64_t h);
+int32_t nais_geoie_train_step(const nais_geoie_params_t* params, int64_t user, const int64_t* hist,
+                              int64_t h, const int64_t* target, const float* labels,
+                              const int64_t* freq, int64_t b, const float* distances,
+                              int64_t dist_ld, float lr, float weight_decay, int32_t* stamp_target,
+                              int32_t* stamp_hist, int32_t tag, float* loss_sum, int32_t* bad_rows,
+                              int32_t* err, float* pred, const nais_geoie_train_grads_t* grads,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int32_t nais_sgd(float* param, const float* grad, int64_t rows, int32_t dim, float lr,
+                 float weight_decay, const int32_t* stamp, int32_t tag, int64_t skip_row,
+                 const int32_t* err, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step of NAIS_basic on one get_NAIS_batch batch (batches.py:24-50):

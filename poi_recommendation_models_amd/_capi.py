@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -36,7 +36,9 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_pair_bound_topk", "nais_pair_refine_topk", "nais_pair_table_bound",
            "nais_pair_bound_topk_widened", "nais_pair_scales", "nais_pair_refine_topk_exact",
            "nais_pair_recompute", "nais_pair_table_bound_queued", "nais_pair_table_bound1_queued",
-           "nais_geoie_table", "nais_geoie_score", "nais_geoie_forward")
+           "nais_geoie_table", "nais_geoie_score", "nais_geoie_forward",
+           "nais_geoie_make_train_batch", "nais_geoie_train_step_workspace_size",
+           "nais_geoie_train_step", "nais_sgd")
 
 
 class NaisGeoIEParams(ctypes.Structure):
@@ -44,6 +46,11 @@ class NaisGeoIEParams(ctypes.Structure):
     _fields_ = [("embed_dim", ctypes.c_int32), ("num_users", ctypes.c_int64),
                 ("num_pois", ctypes.c_int64), ("a", ctypes.c_float), ("b", ctypes.c_float)] + \
         [(n, ctypes.c_void_p) for n in ("user_pref", "poi_pref", "geo_influence", "geo_suscept")]
+
+
+class NaisGeoIETrainGrads(ctypes.Structure):
+    """Mirror of `nais_geoie_train_grads_t` (include/nais.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("user_pref", "poi_pref", "geo_suscept", "geo_influence")]
 
 
 class NaisDotTables(ctypes.Structure):
@@ -271,6 +278,17 @@ def load(path: str | None = None):
     lib.nais_geoie_forward.restype = i32
     lib.nais_geoie_forward.argtypes = [ctypes.POINTER(NaisGeoIEParams), vp, vp, vp, i64, i64, i64, vp,
                                        i64, vp, vp]
+    lib.nais_geoie_make_train_batch.restype = i32
+    lib.nais_geoie_make_train_batch.argtypes = [vp, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp, vp, vp,
+                                                vp, vp, i64, vp, vp]
+    lib.nais_geoie_train_step_workspace_size.restype = sz
+    lib.nais_geoie_train_step_workspace_size.argtypes = [ctypes.POINTER(NaisGeoIEParams), i64, i64]
+    lib.nais_geoie_train_step.restype = i32
+    lib.nais_geoie_train_step.argtypes = [ctypes.POINTER(NaisGeoIEParams), i64, vp, i64, vp, vp, vp, i64,
+                                          vp, i64, f32, f32, vp, vp, i32, vp, vp, vp, vp,
+                                          ctypes.POINTER(NaisGeoIETrainGrads), vp, sz, vp]
+    lib.nais_sgd.restype = i32
+    lib.nais_sgd.argtypes = [vp, vp, i64, i32, f32, f32, vp, i32, i64, vp, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

@@ -998,7 +998,9 @@ class GeoIE(nn.Module):
     With grad disabled (`torch.no_grad()`, as run.py:720-723 evaluates) the forward is the HIP
     kernel `nais_geoie_forward`; with grad enabled it is the reference's own sequence of torch ops
     on the device, so `train_GeoIE`'s loop (run.py:702-715: forward, `loss_function`, `backward()`,
-    SGD step) runs unchanged. A fused training step is not built. Off the ROCm device it raises."""
+    SGD step) runs unchanged. The fused training step (`nais_geoie_train_step`: forward, loss,
+    backward and SGD in one call, with batches built on the device) is `trainer.GeoIETrainer`. Off
+    the ROCm device it raises."""
 
     def __init__(self, user_count, POI_count, emb_dimension, neg_num, a, b):
         super().__init__()

@@ -23,8 +23,14 @@ The per-step arithmetic is the drop-in path's (NAIS_basic train-mode forward + b
 optim.Adagrad), differing only in fp32 summation order; tests/test_gpu_train.py checks both
 against the oracle. Batches follow get_NAIS_batch's distribution (shuffled positives as the
 shared history, num_ng distinct uniform negatives per positive), not Python's random stream.
+
+`GeoIETrainer` is the same treatment of train_GeoIE (run.py:687-715): `nais_geoie_make_train_batch`
+is get_GeoIE_batch (batches.py:204-242) on the device and `nais_geoie_train_step` is forward,
+loss_function, backward and torch.optim.SGD in place on the four embedding tables.
 """
 from __future__ import annotations
+
+import warnings
 
 import numpy as np
 import torch
@@ -245,3 +251,172 @@ class NAISTrainer:
         """torch.optim.Adagrad-style per-parameter state {name: {'step', 'sum'}}."""
         return {k: {"step": torch.tensor(float(self.step_count)), "sum": self.sums[k]}
                 for k in self._names}
+
+
+class GeoIETrainer:
+    """train_GeoIE's loop (run.py:687-715) on the device: `batch()` is get_GeoIE_batch
+    (batches.py:204-242), `step()` is run.py:705-715 (forward, loss_function, backward,
+    torch.optim.SGD(lr, weight_decay) without momentum) updating the model's four tables in
+    place, `epoch()` the loop with one host sync at its end. Distances come from exactly one of
+    `dist_mat` (the reference's P x P matrix, run.py:683) and `poi_coords` ([P, 2] lat / lng)."""
+
+    def __init__(self, model, train_matrix, lr=0.01, weight_decay=0.0, num_ng=4, dist_mat=None,
+                 poi_coords=None):
+        from .geoie import _distance_source
+        from .model import GeoIE
+        if not isinstance(model, GeoIE):
+            raise NotImplementedError(f"GeoIETrainer: {type(model).__name__} is not GeoIE")
+        dev = model._check_device()
+        if int(num_ng) < 1:
+            raise ValueError(f"GeoIETrainer: num_ng must be at least 1, got {num_ng}")
+        if (dist_mat is None) == (poi_coords is None):
+            raise ValueError("GeoIETrainer needs exactly one of dist_mat and poi_coords")
+        self.model, self.dev = model, dev
+        self.csr = device_csr(train_matrix, dev)
+        P = model.POI_count
+        if self.csr.shape[1] != P:
+            raise ValueError(f"train_matrix has {self.csr.shape[1]} POIs, model has {P}")
+        self.coords, self.dist_mat = _distance_source(dev, P, dist_mat, poi_coords)
+        X = train_matrix.tocsr() if not hasattr(train_matrix, "indptr") else train_matrix
+        if not X.has_sorted_indices:   # the order device_csr holds the rows in
+            X = X.sorted_indices()
+        self.data = torch.from_numpy(np.asarray(X.data, dtype=np.float64)).to(dev)
+        self.num_ng, self.lr, self.weight_decay = int(num_ng), float(lr), float(weight_decay)
+        self.step_count = 0
+        self._st_t = torch.zeros(P, dtype=torch.int32, device=dev)
+        self._st_h = torch.zeros(P, dtype=torch.int32, device=dev)
+        self.loss_sum = torch.zeros(1, device=dev)
+        self.bad_rows = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ws = torch.empty(0, dtype=torch.uint8, device=dev)
+        self._bufs = {}
+
+    def _check_user(self, uid):
+        h = int(self.csr.hist_len[uid])
+        if h == 0:   # the reference's reshape raises here (model.py:798)
+            raise ValueError(f"GeoIE: empty history (user {int(uid)})")
+        P = self.csr.shape[1]
+        if h * self.num_ng > P - h:
+            raise ValueError(f"user {int(uid)}: {h} positives x {self.num_ng} negatives exceed the "
+                             f"{P - h} POIs outside the history (get_GeoIE_batch cannot draw them)")
+        return h
+
+    def batch(self, uid, seed=None):
+        """get_GeoIE_batch(train_matrix, P, P, uid, num_ng, dist_mat) on the device: (user_id [b],
+        hist [h], target [b], labels [b], freq [b, 1] int64, distances [b, h] f32); the reference's
+        user_history is hist repeated b times. The buffers are reused by the next call of the
+        same shape."""
+        h = self._check_user(uid)
+        b = h * (1 + self.num_ng)
+        if h not in self._bufs:
+            d = self.dev
+            self._bufs = {h: (torch.empty(b, dtype=torch.int64, device=d),
+                              torch.empty(h, dtype=torch.int64, device=d),
+                              torch.empty(b, dtype=torch.int64, device=d),
+                              torch.empty(b, dtype=torch.float32, device=d),
+                              torch.empty(b, 1, dtype=torch.int64, device=d),
+                              torch.empty(b, h, dtype=torch.float32, device=d))}
+        uidt, hist, tgt, lab, freq, dist = self._bufs[h]
+        uidt.fill_(int(uid))
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        _capi.check(_capi.load().nais_geoie_make_train_batch(
+            self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(), self.data.data_ptr(), int(uid), h,
+            self.csr.shape[1], self.num_ng, seed, _capi.ptr(self.coords), _capi.ptr(self.dist_mat),
+            hist.data_ptr(), tgt.data_ptr(), lab.data_ptr(), freq.data_ptr(), dist.data_ptr(), h,
+            self._err.data_ptr(), _capi.stream_handle(self.dev)), "nais_geoie_make_train_batch")
+        return uidt, hist, tgt, lab, freq, dist
+
+    def step(self, user_id, hist, target, labels, freq, distances, pred=None, grads=None):
+        """One fused step (run.py:705-715) on a batch as batch() returns it, or in the reference's
+        own layout (get_GeoIE_batch: user_history [b, h] repeated rows, user_id [b]). `pred`:
+        optional [b] f32 output; `grads`: optional dict that receives the four row-gradient blocks
+        under the parameter names (UserPreference.weight [D], PoiPreference.weight [b, D],
+        GeoSusceptibility.weight [b, D], GeoInfluence.weight [h, D], rows in batch order)."""
+        m = self.model
+        on_dev = isinstance(user_id, torch.Tensor)
+        dev = m._check_device(user_id if on_dev else None, hist, target, labels, freq, distances)
+        if hist.dim() == 2:
+            hist = hist[0] if hist.shape[0] else hist.new_empty(0)
+        uids = torch.unique(user_id.reshape(-1)).tolist() if on_dev else [int(user_id)]
+        if len(uids) != 1:
+            raise ValueError(f"GeoIETrainer.step: one batch is one user, got users {uids}")
+        hist = hist.reshape(-1).to(torch.int64).contiguous()
+        target = target.reshape(-1).to(torch.int64).contiguous()
+        labels = labels.reshape(-1).to(torch.float32).contiguous()
+        freq = freq.reshape(-1).to(torch.int64).contiguous()
+        b, h = target.numel(), hist.numel()
+        if h == 0:
+            raise ValueError(f"GeoIE: empty history (user {uids[0]})")
+        distances = distances.to(torch.float32)
+        if tuple(distances.shape) != (b, h) or labels.numel() != b or freq.numel() != b or b == 0:
+            raise ValueError(f"labels / freq must hold b = {b} rows (b >= 1) and distances [b, h = {h}]; "
+                             f"got {labels.numel()}, {freq.numel()}, {tuple(distances.shape)}")
+        if distances.stride(1) != 1:
+            distances = distances.contiguous()
+        D = int(m.emb_dimension)
+        gs = _capi.NaisGeoIETrainGrads()
+        if grads is not None:
+            gu = torch.empty(D, device=dev)
+            gp, gh = torch.empty(b, D, device=dev), torch.empty(b, D, device=dev)
+            gg = torch.empty(h, D, device=dev)
+            grads.update({"UserPreference.weight": gu, "PoiPreference.weight": gp,
+                          "GeoSusceptibility.weight": gh, "GeoInfluence.weight": gg})
+            gs.user_pref, gs.poi_pref = gu.data_ptr(), gp.data_ptr()
+            gs.geo_suscept, gs.geo_influence = gh.data_ptr(), gg.data_ptr()
+        if pred is not None and (pred.dtype != torch.float32 or pred.numel() != b or not pred.is_contiguous()):
+            raise ValueError("pred must be a contiguous float32 tensor of b elements")
+        lib = _capi.load()
+        prm = m.geoie_params()
+        need = lib.nais_geoie_train_step_workspace_size(prm, b, h)
+        if self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=dev)
+        self.step_count += 1
+        _capi.check(lib.nais_geoie_train_step(
+            prm, int(uids[0]), hist.data_ptr(), h, target.data_ptr(), labels.data_ptr(), freq.data_ptr(),
+            b, distances.data_ptr(), distances.stride(0), self.lr, self.weight_decay,
+            self._st_t.data_ptr(), self._st_h.data_ptr(), self.step_count, self.loss_sum.data_ptr(),
+            self.bad_rows.data_ptr(), self._err.data_ptr(), _capi.ptr(pred),
+            gs if grads is not None else None, self._ws.data_ptr(), self._ws.numel(),
+            _capi.stream_handle(dev)), "nais_geoie_train_step")
+        self._bump_versions()
+
+    def _step_uid(self, uid, batch):
+        """step() on a batch() result: the user is known, so no device read of user_id."""
+        return self.step(int(uid), *batch[1:])
+
+    def _bump_versions(self):
+        """As NAISTrainer._bump_versions: the step writes through raw pointers."""
+        for q in self.model.parameters():
+            increment_version(q)
+
+    def epoch(self, users=None, shuffle=True):
+        """run.py:694-715 over `users` (default: every user, shuffled as run.py:694-696). Returns
+        train_loss (run.py:714), read with the epoch's one host sync."""
+        if users is None:
+            users = np.arange(self.csr.shape[0])
+        users = np.asarray(users, dtype=np.int64)
+        if shuffle:
+            users = users[torch.randperm(len(users)).numpy()]
+        self.model.train()
+        self.loss_sum.zero_()
+        for u in users.tolist():
+            self._step_uid(u, self.batch(u))
+        return self.finish()
+
+    def finish(self):
+        """Host sync: the accumulated loss. Raises if a step saw a repeated target or history
+        entry, an id outside the catalog, or a history length that disagrees with the CSR (that
+        step and every later one left the tables untouched); warns if a loss term was not finite
+        (the reference prints its tensors and carries on, model.py:820-826)."""
+        err = int(self._err.item())
+        if err:
+            self._err.zero_()
+            raise RuntimeError("GeoIETrainer: a batch had a repeated target or history entry, an id "
+                               "outside the catalog, or a history length that disagrees with the CSR "
+                               f"(code {err}); that step and the later ones were not applied")
+        bad = int(self.bad_rows.item())
+        if bad:
+            self.bad_rows.zero_()
+            warnings.warn(f"GeoIE: {bad} row(s) with a non-finite loss term (model.py:820)", RuntimeWarning)
+        return float(self.loss_sum.item())
