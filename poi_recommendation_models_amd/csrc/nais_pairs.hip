@@ -620,6 +620,9 @@ struct Bounds {
 // hence |e s - es~| <= (2^-7 + eta2) |es~| + e^ (1 + 2^-7)(1 + eta) ds per term, eta2 = 1.02 eta +
 // 2^-21 (eta on a |e~ s~| that is up to (1 + 2^-7) |es~|, and the two fp32 products' roundings).
 // Zeros: the bounds of the split16 route, bit for bit.
+// tests/test_gpu_bound_intervals.py holds make_bounds / upper_score / lower_score (and may_reach,
+// the lists) to this derivation: every candidate's interval against its exact score, on tables
+// built to sit at the ends of each margin. Change a margin here and run it.
 struct Widen {
   float eta, eta2, ds;
 };
