@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 19   /* 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 20   /* 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -362,7 +362,48 @@ int32_t nais_pair_refine_topk(const uint32_t* ex, int64_t block_stride,
  *                      the same items, col0-block geometry and scales (tests/test_gpu_ondemand_refine.py).
  * Shapes of the last three: NAIS_basic at precision fp16x6, embed_dim 32 or 64, hidden <= 64
  * (NAIS_E_UNSUPPORTED otherwise; the caller keeps the split16 route).
+ *
+ * "q16" (ABI 20; DESIGN.md (d) "Block-scaled 16-bit pair words"): the one-product bound table in
+ * 16-bit pair words with one scale pair per (row, 16 columns) -- 1152 bytes per 512-column row
+ * where the hi words take 2048. One buffer per table block; row r starts at byte r * pitch,
+ *   pitch = nais_q16_pitch(ld) = 4 * ceil(ld / 16) + 2 * ld, rounded up to 128  (ld = 512: 1152).
+ * A row holds ceil(ld / 16) scale words (uint32: bits 31..16 = q_s, bits 15..0 = q_e, each the top
+ * 16 bits of a non-negative fp32, the low 16 read as 0), then ld pair words (uint16: low byte m_e
+ * in 0..255, high byte m_s + 128 with m_s in -128..127). Column x of the block belongs to group
+ * x / 16. For the pair values (e, p = e * s) nais_pair_table_bound1_queued computes:
+ *   (m_e - 2^-14) q_e <= e < (m_e + 1 + 2^-14) q_e,   (m_s - 2^-14) q_s <= p < (m_s + 1 + 2^-14) q_s
+ * (the 2^-14, in units of the scale, is the slack of the quantiser's v_rcp_f32 and one fp32
+ * rounding on a quotient below 256; the gather's margins hold it).
+ * Scales: with M_e = the largest e and M_s the largest |p| over the group's columns inside the
+ * launch's [col0, col0 + cols) (a ragged last group counts its valid columns only), q_e is
+ * M_e / 255 and q_s is M_s / 127, each times (1 + 2^-7)(1 + 2^-13) and truncated to 16 bits: no
+ * less than the quotient and less than (1 + 2^-6) of it. A quotient below 2^-100 gets the scale
+ * 2^-100 (below fp32's normal range the 16 bits no longer resolve 2^-6 and the reciprocal
+ * overflows; the contract above holds all the same, and pairs that small bound nothing under the
+ * hi words either once their sum leaves the normal range); an all-zero group stores scale 0 and
+ * the words 0 / 128; a group with a NaN or an infinity stores a non-finite scale (its words are
+ * then meaningless, and the gather refines every candidate whose sums touch it). Pair words past
+ * `cols` and the scale words of groups wholly past it are not written.
+ *   nais_pair_table_bound1_q16_queued  nais_pair_table_bound1_queued writing that format: q16 is
+ *                      the block [num_items rows], pitch must be nais_q16_pitch(ld). Same kernel,
+ *                      same (e, p) before quantisation; work = NULL selects the fixed grid, whose
+ *                      bytes equal the queued ones.
+ *   nais_pair_bound_topk_q16  nais_pair_bound_topk_widened reading that format. Other arguments,
+ *                      lists, survivors and the overflow mark as there; the intervals are wider
+ *                      by the quantisation (nais_pairs.hip, make_bounds_q16).
  */
+int64_t nais_q16_pitch(int64_t ld);   /* the row pitch above, in bytes (0 for ld <= 0) */
+int32_t nais_pair_table_bound1_q16_queued(const nais_params_t* params, const int64_t* items,
+                                          int64_t num_items, int64_t col0, int64_t cols,
+                                          const int64_t* region_of, const double* coords,
+                                          const double* latlon_mat, void* q16, int64_t ld,
+                                          int64_t pitch, int32_t* work, void* stream);
+int32_t nais_pair_bound_topk_q16(const void* q16, int64_t ld, int64_t pitch, const int32_t* rowmap,
+                                 const int64_t* indptr, const int64_t* indices, const int32_t* users,
+                                 int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
+                                 uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv,
+                                 int32_t* surv_count, int32_t surv_cap, const int32_t* entry_rows,
+                                 const int64_t* spans, const float* widen, int32_t* work, void* stream);
 int32_t nais_pair_table_bound(const nais_params_t* params, const int64_t* items, int64_t num_items,
                               int64_t col0, int64_t cols, const int64_t* region_of,
                               const double* coords, const double* latlon_mat, uint32_t* hi,

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -36,6 +36,7 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_pair_bound_topk", "nais_pair_refine_topk", "nais_pair_table_bound",
            "nais_pair_bound_topk_widened", "nais_pair_scales", "nais_pair_refine_topk_exact",
            "nais_pair_recompute", "nais_pair_table_bound_queued", "nais_pair_table_bound1_queued",
+           "nais_q16_pitch", "nais_pair_table_bound1_q16_queued", "nais_pair_bound_topk_q16",
            "nais_geoie_table", "nais_geoie_score", "nais_geoie_forward",
            "nais_geoie_make_train_batch", "nais_geoie_train_step_workspace_size",
            "nais_geoie_train_step", "nais_sgd")
@@ -261,6 +262,14 @@ def load(path: str | None = None):
     lib.nais_pair_bound_topk_widened.restype = i32
     lib.nais_pair_bound_topk_widened.argtypes = [vp, i64, vp, vp, vp, vp, i32, i64, i64, f32, i32, vp, vp,
                                                  vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.nais_q16_pitch.restype = i64
+    lib.nais_q16_pitch.argtypes = [i64]
+    lib.nais_pair_table_bound1_q16_queued.restype = i32
+    lib.nais_pair_table_bound1_q16_queued.argtypes = [ctypes.POINTER(NaisParams), vp, i64, i64, i64, vp,
+                                                      vp, vp, vp, i64, i64, vp, vp]
+    lib.nais_pair_bound_topk_q16.restype = i32
+    lib.nais_pair_bound_topk_q16.argtypes = [vp, i64, i64, vp, vp, vp, vp, i32, i64, i64, f32, i32, vp,
+                                             vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.nais_pair_scales.restype = i32
     lib.nais_pair_scales.argtypes = [ctypes.POINTER(NaisParams), vp, i64, i64, i64, i64, vp, vp, vp]
     lib.nais_pair_refine_topk_exact.restype = i32

@@ -294,6 +294,17 @@ X3Q_GATHER_MARGIN = 1.14
 # cliff. One job on one device size, as above.
 X1Q_RATE = 6.0e14
 X1Q_GATHER_MARGIN = 1.34
+# The same table writing q16 blocks (ABI 20) under the q16 gather, fitted the same way on config 4
+# (profiles/q16, DESIGN.md (d) "Block-scaled 16-bit pair words"): the quantising tail costs the
+# tables 7 % (36.7 CU-s where they bound the step: 269.8 / 240.8 / 229.7 ms busy on 136 / 152 / 160
+# CUs), 5.7e14 FLOP/s on the whole chip. The gathers read 2.25 bytes per pair and are now bound by
+# their own VALU work, not the memory side: 195.3 / 201.6 / 210.0 / 220.0 ms busy on 120 / 112 / 104 /
+# 96 CUs, about 95 ms + 12.0 CU-s / CUs, and steeply worse below three whole XCDs (268 ms on 88,
+# 300 on 72). The step is lowest at 160 / 96 (283.1-283.8 ms in three alternating rounds; 158:
+# 284.2-284.5, 162: 286.2-286.7, 156: 287.9-289.2, 164: 291.3-291.9, 166: 302.5-302.9); the margin
+# puts the three-term fit (at 2.25 bytes) there. One job on one device size, as above.
+X1Q16_RATE = 5.7e14
+X1Q16_GATHER_MARGIN = 1.16
 # Bounded gather + exact refine (round 6; include/nais.h nais_pair_bound_topk): the fused top-k
 # from split16 tables -- the gather streams only their hi halves (4 bytes per history entry and
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
@@ -325,6 +336,15 @@ PAIR_ONDEMAND_ETA_MAX = 2.0 ** -9
 # its own rule, else split16. "0" forces the three-product form (A/B).
 PAIR_ONDEMAND_ONE_PRODUCT = os.environ.get("NAIS_PAIR_ONDEMAND_ONE_PRODUCT", "1") != "0"
 PAIR_ONDEMAND_ETA1_MAX = 2.0 ** -7
+# Block-scaled 16-bit pair words under the one-product form (ABI 20; include/nais.h "q16", DESIGN.md
+# (d) "Block-scaled 16-bit pair words"): the ring holds q16 blocks -- 2.25 bytes per (table row,
+# column) where the hi words take 4 -- written by nais_pair_table_bound1_q16_queued and gathered by
+# nais_pair_bound_topk_q16, whose intervals hold the quantisation. Same lists, ids and score bits.
+# Taken wherever the one-product form runs; "0" keeps the hi words (A/B). One thing the hi words
+# do and q16 blocks do not: scales stop at 2^-100, so a model whose e = exp(a) lies below about
+# 2^-100 (attention logits under -69) gets no finite interval for those pairs and refines their
+# candidates -- correct, but slow; such a model should run with the knob off.
+PAIR_BOUND_Q16 = os.environ.get("NAIS_PAIR_BOUND_Q16", "1") != "0"
 PAIR_SURV_CAP = 1024            # survivor keys per user (compacted by the current bound when full)
 # the bounded gather / refine get each CSR entry's table row and each slot's history span (ABI 14:
 # shorter chains of dependent loads); "0" passes NULL (A/B only). Per gather launch 2.272 -> 2.224
@@ -334,7 +354,7 @@ PAIR_BOUNDED_STRIPE = 512       # columns per bounded-gather wave (nais_pairs.hi
 _masked: dict = {}
 
 
-def bounded_gather_cu_seconds(entries, NC, users, k):
+def bounded_gather_cu_seconds(entries, NC, users, k, bytes_per_pair=4.0):
     """CU-seconds of one job's bounded gathers (nais_pair_bound_topk, one launch per 512-column
     stripe), fitted on the measured launches (profiles/r6/split_world, profiles/r6/configs):
       entries x NC x 4 B / 90.4 GB/s   the hi words streamed (Infinity-Cache served)
@@ -346,10 +366,10 @@ def bounded_gather_cu_seconds(entries, NC, users, k):
     the per-user terms on fewer bytes. The per-user term is latency: a chain of dependent loads at
     a few waves per SIMD. The per-entry rows, the per-slot spans and 4 rows in flight (4 waves per
     SIMD) brought it to 512 ns: config 4 2.168 ms x 68 CUs, N = 8 2.28 ms x 80 CUs per launch
-    (profiles/r6/chains_ab)."""
+    (profiles/r6/chains_ab). `bytes_per_pair`: 2.25 for q16 blocks (auto_table_cus's q16 branch)."""
     launches = np.ceil(NC / PAIR_BOUNDED_STRIPE)
     ins = k * (1.0 + np.log(max(float(NC), float(k)) / k))
-    return entries * NC * 4.0 / 90.4e9 + 512e-9 * users * launches + 68e-9 * users * ins
+    return entries * NC * bytes_per_pair / 90.4e9 + 512e-9 * users * launches + 68e-9 * users * ins
 
 
 def ondemand_widening(model, products=3):
@@ -443,7 +463,7 @@ def _ondemand_shape(model, prm):
 
 
 def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, work_queues=True,
-                   gather_bytes=8, k=None, users=None, products=None, table_queue=False):
+                   gather_bytes=8, k=None, users=None, products=None, table_queue=False, q16=False):
     """CUs for the table stream (the rest gather), in steps of ncu / 8 (counts off a multiple of 32
     leave a shader engine short and lose -- DESIGN.md, CU split), from a cost model fitted
     on config 4 and config 5 (profiles/r1/cfg5p/, re-fitted in round 3 on the fp16x6 tables:
@@ -465,6 +485,10 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
 
     `products=1` with `table_queue`: the one-product-logit bound table (ABI 17) as a work queue,
     at its own fitted rate (X1Q_RATE) in 2-CU steps.
+
+    `q16` with `products=1` and `table_queue`: the ring holds q16 blocks (ABI 20): 2.25 gathered
+    bytes per pair, the table at the rate its quantising tail leaves it (X1Q16_RATE) and the
+    gather margin fitted on the q16 sweep (X1Q16_GATHER_MARGIN). Ignored on every other route.
 
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
@@ -505,6 +529,10 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     t_tab = J * NC * 2.0 * H * din_k * products / (1.3e14 if products == 1 else rate)
     if x1q:
         t_tab = J * NC * 2.0 * H * din_k / X1Q_RATE
+    q16 = bool(q16) and x1q
+    if q16:
+        t_tab = J * NC * 2.0 * H * din_k / X1Q16_RATE
+        gbytes = entries * NC * 2.25
     if x6n and dist:
         # the distance K-step: 2 v_mfma_f32_16x16x1_4b_f32 (32 cycles each) per PAIR of 16-hidden
         # blocks beside their 2 * 12 * D / 32 f16 MFMAs (16 cycles each): 1 + 16 / (3 D) matrix time
@@ -534,8 +562,12 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
             per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k)
         if x3q:
             per_cu /= X3Q_GATHER_MARGIN
-        if x1q:
+        if x1q and not q16:
             per_cu /= X1Q_GATHER_MARGIN
+        if q16:
+            if users and k:
+                per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k, 2.25)
+            per_cu /= X1Q16_GATHER_MARGIN
     cap = 7.5e12   # the memory side's rate for the gather, chip-wide
     best, best_t = ncu // 2, None
     for n in range((ncu // 4 + step - 1) // step * step, ncu - step + 1, step):
@@ -704,6 +736,8 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
         pri_coords = torch.as_tensor(np.ascontiguousarray(pc, dtype=np.float64)).to(dev)
         prior_flags = _capi.PRIOR_FINITE if _prior_entries_finite(pa, pb) else 0
     pr_of = {}   # column-block table -> its float64 pr_d table (prior only)
+    q16 = [False]    # the pass's ring holds q16 blocks (PAIR_BOUND_Q16 on the one-product form)
+    qpitch = [0]     # ... of this row pitch in bytes
 
     # work-queue counters (PAIR_WORK_QUEUE): one int32 per stream, each used stream-ordered (the
     # launch zeroes its counter itself, behind the stream's previous launch). On for a split off
@@ -726,6 +760,12 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
 
     def table(tab, c0, w, stream_):
         if isinstance(tab, tuple) and len(tab) == 1:   # on-demand refine: hi words alone
+            if ond_products == 1 and q16[0]:   # ... in q16 words (ABI 20)
+                _capi.check(lib.nais_pair_table_bound1_q16_queued(
+                    prm, items.data_ptr(), J, c0, w, _capi.ptr(reg), _capi.ptr(cor), _capi.ptr(llm),
+                    tab[0].data_ptr(), ld, qpitch[0], wq(stream_), stream_),
+                    "nais_pair_table_bound1_q16_queued")
+                return
             if ond_products == 1:   # one f16 product per logit term (ABI 17)
                 _capi.check(lib.nais_pair_table_bound1_queued(
                     prm, items.data_ptr(), J, c0, w, _capi.ptr(reg), _capi.ptr(cor), _capi.ptr(llm),
@@ -782,6 +822,15 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 b = m if b is None else b
                 if b <= a:
                     return
+                if bnd[0] and q16[0]:
+                    _capi.check(lib.nais_pair_bound_topk_q16(
+                        tab[0].data_ptr(), ld, qpitch[0], rowmap.data_ptr(), csr.indptr.data_ptr(),
+                        csr.indices.data_ptr(), u_dev.data_ptr() + 4 * a, b - a, c0, w, float(model.beta), k,
+                        lokeys.data_ptr() + 8 * k * a, locount.data_ptr() + 4 * a,
+                        surv.data_ptr() + 8 * PAIR_SURV_CAP * a, scount.data_ptr() + 4 * a, PAIR_SURV_CAP,
+                        _capi.ptr(erows), spans.data_ptr() + 16 * a if spans is not None else None,
+                        ond.data_ptr(), wq(stream_), stream_), "nais_pair_bound_topk_q16")
+                    return
                 if bnd[0]:
                     _capi.check(lib.nais_pair_bound_topk_widened(
                         tab[0].data_ptr(), ld, rowmap.data_ptr(), csr.indptr.data_ptr(), csr.indices.data_ptr(),
@@ -837,12 +886,20 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                 if ond is not None:
                     ondm[0] = bool(agree_min(int(ondm[0]), dev, tau_group))
             bnd[0] = bnd[0] or ondm[0]
+            # q16 blocks in the ring (never larger than the hi words the sizing above assumed)
+            q16[0] = ondm[0] and ond_products == 1 and PAIR_BOUND_Q16
+            qpitch[0] = int(lib.nais_q16_pitch(ld)) if q16[0] else 0
             if events is not None:
                 events.append(("pair_route", None, None, "ondemand" if ondm[0] else
                                ("split16" if bnd[0] else "exact")))
+                if ondm[0]:
+                    events.append(("ondemand_words", None, None, "q16" if q16[0] else "hi"))
             if bnd[0]:
-                if ondm[0]:   # a ring of hi-word buffers [J, ld], reused behind their gathers
+                if q16[0]:    # a ring of q16 blocks [J, pitch bytes], reused behind their gathers
+                    ring = [torch.empty(J, qpitch[0], dtype=torch.uint8, device=dev) for _ in range(nring)]
+                elif ondm[0]:   # a ring of hi-word buffers [J, ld], reused behind their gathers
                     ring = [torch.empty(J, ld, dtype=torch.int32, device=dev) for _ in range(nring)]
+                if ondm[0]:
                     ring_done = [None] * nring
                     rowsc = torch.empty(max(J, 1), 2, dtype=torch.float32, device=dev)
                     colsc = torch.empty(NC, dtype=torch.float32, device=dev)
@@ -873,7 +930,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                                         J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
                                         users=m, products=ond_products if ondm[0] else None,
-                                        table_queue=ondm[0])
+                                        table_queue=ondm[0], q16=q16[0])
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
             # the on-demand route runs its streams as queues on the engine grid too: config 4 at
             # 160 table CUs ran level with 162 as a queue, 393.3 ms on the fixed grid against

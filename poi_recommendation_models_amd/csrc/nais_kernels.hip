@@ -80,6 +80,11 @@ struct TableOut {
   // v_perm_b32), es the exact (e, e*s) pairs with row pitch 2 * ld (ex = 1)
   uint32_t sel_e = NAIS_SEL_E;
   int32_t ex = 0;
+  // the q16 form (include/nais.h; catalog_score_x3b_kernel's Q16): e is the block's base, row
+  // pitch qpitch bytes, a row's pair words from byte qpairs. Last, so every other form's
+  // arguments stay where they were.
+  int64_t qpitch = 0;
+  int32_t qpairs = 0;
 };
 // the pair's two terms for item row `row` (relative to the launch's base) and column offset x
 __device__ __forceinline__ void tab_put(const TableOut& t, int64_t row, int64_t x, float e, float es) {
@@ -560,6 +565,52 @@ __device__ __forceinline__ floatx16 mfma_pieces(const half8 (&a)[NPC], const hal
 
 // Both lane halves' values of v in every lane, by one v_permlane32_swap (VALU, no LDS):
 // .x = v[lane & 31], .y = v[32 + (lane & 31)]; .x + .y == v + shfl_xor(v, 32) exactly.
+// q16 (include/nais.h): one pair's words from (e, p = e * s), held alike by lane l < 32 (column
+// x0 + l of the wave's 32) and lane l + 32. The lower half quantises e and the upper half p, so
+// the group maximum, the scale and the reciprocal are computed once per lane for both values:
+//   v = e or |p| as bits (0 where the column is outside the launch: maxima over valid columns only);
+//   M = the maximum over the lane's row of 16 (4 DPP row rotations; UNSIGNED, so a NaN, whose
+//       bits lie above infinity's, makes the scale non-finite instead of being dropped by v_max_f32);
+//   q = M * c truncated to 16 bits, c = (1 + 2^-7)(1 + 2^-13) / 255 or / 127: at least the
+//       quotient (the truncation takes less than 2^-7, the roundings of c and of the product
+//       2^-23) and below (1 + 2^-6) of it; at least 2^-100; 0 for M = 0;
+//   m = trunc(e / q) or trunc(p / q + 128), as one v_rcp_f32 and one v_fma_f32: within 2^-14 of
+//       the real quotient (2^-22 of a value below 256, and half an ulp of 256), clamped to 0..255
+//       (reached only with a non-finite scale, whose words mean nothing).
+// One v_permlane32_swap brings (q_s | m_s + 128) to the lower half; two v_perm_b32 cut the words.
+// Every lane of the wave must call it. About 20 VALU per lane and item (the reciprocal takes 4
+// issue slots), and 7 s_nop for the DPP hazards.
+struct Q16Words {
+  uint32_t pair, scale;   // valid in lanes 0..31
+};
+__device__ __forceinline__ uint32_t q16_row_max(uint32_t v) {
+#define NAIS_ROR_MAX(n) \
+  v = max(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x120 + (n), 0xF, 0xF, false))
+  NAIS_ROR_MAX(8);
+  NAIS_ROR_MAX(4);
+  NAIS_ROR_MAX(2);
+  NAIS_ROR_MAX(1);
+#undef NAIS_ROR_MAX
+  return v;
+}
+__device__ __forceinline__ Q16Words q16_words(float e, float p, bool valid, int hh) {
+  constexpr float C255 = (float)((1.0 + 0x1p-7) * (1.0 + 0x1p-13) / 255.0);
+  constexpr float C127 = (float)((1.0 + 0x1p-7) * (1.0 + 0x1p-13) / 127.0);
+  const float x = hh ? p : e;
+  const uint32_t M = q16_row_max(valid ? (__float_as_uint(x) & 0x7FFFFFFFu) : 0u);
+  uint32_t qb = __float_as_uint(__uint_as_float(M) * (hh ? C127 : C255)) & 0xFFFF0000u;
+  qb = max(qb, 0x0D800000u);   // 2^-100 (unsigned: a NaN stays)
+  qb = M ? qb : 0u;
+  const float r = M ? __builtin_amdgcn_rcpf(__uint_as_float(qb)) : 0.f;
+  const float u = __builtin_amdgcn_fmed3f(fmaf(x, r, hh ? 128.f : 0.f), 0.f, 255.f);
+  const uint32_t pk = qb | (uint32_t)u;
+  const auto sw = __builtin_amdgcn_permlane32_swap(pk, pk, false, false);   // (lower half's, upper half's)
+  Q16Words w;
+  w.pair = __builtin_amdgcn_perm(sw[1], sw[0], 0x0C0C0400u);
+  w.scale = __builtin_amdgcn_perm(sw[1], sw[0], NAIS_SEL_HI);
+  return w;
+}
+
 __device__ __forceinline__ float2 lane_halves(float v) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return make_float2(__uint_as_float(r[0]), __uint_as_float(r[1]));
@@ -940,7 +991,10 @@ struct CfgB {
 // ~2^-10 of its terms instead of 2^-21; the s tile keeps its NPC pieces and products, so s has the
 // bits of the ONE = false instance. Scales, accumulator start, epilogue, tail and work loop are
 // shared. false compiles it away, as QUEUE.
-template <int DH, int HB, int VAR, int NW, int NPC, bool QUEUE = false, bool ONE = false>
+// Q16: the q16 output form of the ONE table (nais_pair_table_bound1_q16_queued): the tail
+// quantises the pair (q16_words) and stores one 2-byte pair word per column and one scale word per
+// 16 columns instead of the hi word. false compiles it away.
+template <int DH, int HB, int VAR, int NW, int NPC, bool QUEUE = false, bool ONE = false, bool Q16 = false>
 __global__ void __launch_bounds__(NW * 64, NW >= 8 ? 1 : 8 / NW)   // >= 2 waves per SIMD per CU
 catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
                          const int64_t* __restrict__ indices, const int32_t* __restrict__ users,
@@ -956,6 +1010,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   constexpr bool PIPE = C::PIPE;
   static_assert(!ONE || (NPC == 2 && PIPE && !DIST),
                 "one-product logits: the pipelined fp16x3 shapes, no distance inputs");
+  static_assert(!Q16 || ONE, "q16 words: the one-product bound table only");
   // s = h_j . t_c for the chunk's 32 items on the matrix pipe (one 32x32 tile per wave and chunk,
   // the same split-fp16 3-product scheme) instead of a 2*DH-term VALU dot per item and lane
   constexpr bool SMF = JCB == 32;
@@ -1163,6 +1218,18 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     }
     const bool keep = hid[pj] != (int32_t)c;
     const float e = expf(a) * (keep ? 1.f : 0.f);
+    if constexpr (Q16) {   // live is wave-uniform: the cross-lane steps of q16_words run whole
+      if (live) {
+        const Q16Words qw = q16_words(e, e * sv, valid, hh);
+        if (valid && hh == 0) {
+          const int64_t x = c - tab.col0;
+          char* row = reinterpret_cast<char*>(tab.e) + (hbeg + j0 + pj) * tab.qpitch;
+          reinterpret_cast<uint16_t*>(row + tab.qpairs)[x] = (uint16_t)qw.pair;
+          if ((lane & 15) == 0) reinterpret_cast<uint32_t*>(row)[x >> 4] = qw.scale;
+        }
+      }
+      return;
+    }
     if (live) {
       if (tab.e) {
         if (valid && hh == 0) {
@@ -2921,13 +2988,13 @@ int launch_catalog_x3b(const DevParams& d, const int64_t* indptr, const int64_t*
 // The one-product-logit bound table (catalog_score_x3b_kernel<..., ONE = true>): pair-table mode of
 // NAIS_basic at padded D in {32, 64}, H <= 64 -- the shapes the on-demand refine covers -- as a
 // work queue with tab.work, on the fixed grid without.
-template <int DH, int HB>
+template <int DH, int HB, bool Q16 = false>
 int launch_x3b_one(const DevParams& d, const int64_t* indices, int ng, hipStream_t stream,
                    const TableOut& tab) {
   constexpr int NW = WAVES, VAR = NAIS_VARIANT_BASIC;
   const size_t lds = CfgB<DH, HB, false, NW, 2, 1>::BYTES;
-  auto kern = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, false, true>;
-  auto kq = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, true, true>;
+  auto kern = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, false, true, Q16>;
+  auto kq = catalog_score_x3b_kernel<DH, HB, VAR, NW, 2, true, true, Q16>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -3187,7 +3254,9 @@ namespace {
 int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64_t num_items,
                         int64_t col0, int64_t cols, const int64_t* region_of, const double* coords,
                         const double* latlon_mat, float* e, float* es, int64_t ld, int32_t* work,
-                        void* stream, bool split = false, bool bound = false, bool one = false) {
+                        void* stream, bool split = false, bool bound = false, bool one = false,
+                        int64_t qpitch = 0) {
+  // qpitch > 0 (with one): e is a q16 block of that row pitch in bytes (nais_pair_table_bound1_q16_queued)
   // bound: the hi words of the split16 form alone, from the 3-product (fp16x3) kernels whatever
   // params->precision says -- es stays null and no (e, e*s) pair is stored (nais_pair_table_bound)
   // one (with bound): from the one-product-logit form of that kernel (nais_pair_table_bound1_queued)
@@ -3199,6 +3268,9 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
   if (num_items == 0 || cols == 0) return NAIS_OK;
   if (!items || !e || (!es && !bound)) return fail(NAIS_E_INVALID, "missing pointer");
   if (ld < cols) return fail(NAIS_E_INVALID, "ld < cols");
+  if (qpitch && (!one || ld > (1 << 24) || qpitch != nais_q16_pitch(ld) ||
+                 (reinterpret_cast<uintptr_t>(e) & 3) != 0))
+    return fail(NAIS_E_INVALID, "q16: pitch must be nais_q16_pitch(ld) and the block 4-byte aligned");
   if ((params->variant == NAIS_VARIANT_REGION || params->variant == NAIS_VARIANT_REGION_DISTANCE) &&
       !region_of)
     return fail(NAIS_E_INVALID, "region variants need region_of");
@@ -3233,7 +3305,15 @@ int32_t pair_table_impl(const nais_params_t* params, const int64_t* items, int64
     tab.es = es ? es + base * ld * (split ? 2 : 1) : nullptr;
     tab.col0 = col0;
     const int ng = (int)((tab.nitems + tab.gi - 1) / tab.gi);
-    if (one)
+    if (qpitch) {
+      tab.e = reinterpret_cast<float*>(reinterpret_cast<char*>(e) + base * qpitch);
+      tab.qpitch = qpitch;
+      tab.qpairs = (int32_t)(4 * ((ld + 15) / 16));
+      rc = sh.DH == 16 ? (sh.HB == 1 ? launch_x3b_one<16, 1, true>(d, items + base, ng, st, tab)
+                                     : launch_x3b_one<16, 2, true>(d, items + base, ng, st, tab))
+                       : (sh.HB == 1 ? launch_x3b_one<32, 1, true>(d, items + base, ng, st, tab)
+                                     : launch_x3b_one<32, 2, true>(d, items + base, ng, st, tab));
+    } else if (one)
       rc = sh.DH == 16 ? (sh.HB == 1 ? launch_x3b_one<16, 1>(d, items + base, ng, st, tab)
                                      : launch_x3b_one<16, 2>(d, items + base, ng, st, tab))
                        : (sh.HB == 1 ? launch_x3b_one<32, 1>(d, items + base, ng, st, tab)
@@ -3294,6 +3374,17 @@ int32_t nais_pair_table_bound1_queued(const nais_params_t* params, const int64_t
                                       int32_t* work, void* stream) {
   return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
                          reinterpret_cast<float*>(hi), nullptr, ld, work, stream, false, true, true);
+}
+
+int32_t nais_pair_table_bound1_q16_queued(const nais_params_t* params, const int64_t* items,
+                                          int64_t num_items, int64_t col0, int64_t cols,
+                                          const int64_t* region_of, const double* coords,
+                                          const double* latlon_mat, void* q16, int64_t ld,
+                                          int64_t pitch, int32_t* work, void* stream) {
+  if (pitch <= 0) return fail(NAIS_E_INVALID, "q16: pitch must be nais_q16_pitch(ld)");
+  return pair_table_impl(params, items, num_items, col0, cols, region_of, coords, latlon_mat,
+                         reinterpret_cast<float*>(q16), nullptr, ld, work, stream, false, true, true,
+                         pitch);
 }
 
 int32_t nais_pair_scales(const nais_params_t* params, const int64_t* items, int64_t num_items,

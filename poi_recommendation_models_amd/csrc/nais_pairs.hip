@@ -599,6 +599,75 @@ __device__ __forceinline__ void bound_rows(const uint32_t* __restrict__ HI, int6
   }
 }
 
+// The same sums from a q16 block (include/nais.h, "q16"): per row the lane reads its 8 pair words
+// (one 16-byte load; low byte m_e, high byte m_s + 128) and the scale word of their group of 16
+// columns (q_s in the top half, q_e in the low half, each the top 16 bits of an fp32), and adds
+//   S += m_e q_e,  N += (m_s + 128) q_s  (per column),  Q += (q_e, q_s)  (per lane: one group)
+// -- every product exact in fp32 (8 x 8 significant bits), the bytes converted by
+// v_cvt_f32_ubyteN, the sums by v_pk_fma_f32: 3 VALU per pair and 3 per row. The caller takes
+// 128 Qs off N. BGU8 rows in flight: the bytes in flight of BGU hi rows.
+// recbytes: the row's bytes up to the launch's last column (later ones read as 0; no candidates).
+constexpr int BGU8 = 2 * BGU;
+// A/B builds only (profiles/q16, "per-column A"): 1 also sums A += |m_s| q_s per column (a subtract
+// and an fma more per pair), and the interval takes A = (that + Qs)(1 + 2^-10) instead of the group
+// bound 128 Qs. Measured slower at every CU split; the product library is built with 0.
+#ifndef NAIS_Q16_COLA
+#define NAIS_Q16_COLA 0
+#endif
+constexpr int QNA = NAIS_Q16_COLA ? BCPL : 1;
+#ifndef NAIS_Q16_WAVES
+#define NAIS_Q16_WAVES 4   // waves per SIMD asked of the q16 gather (A/B: 3 keeps the per-column A out of scratch)
+#endif
+__device__ __forceinline__ void bound_rows_q16(const uint32_t* __restrict__ Q, int64_t pitch4, int32_t mrow,
+                                               int jn, uint32_t recbytes, uint32_t voff, uint32_t soff,
+                                               f2v (&S)[BCPL / 2], f2v (&N)[BCPL / 2], f2v& QQ,
+                                               float (&A)[QNA]) {
+  auto row = [&](int jj) __attribute__((always_inline)) {
+    const int64_t r = __builtin_amdgcn_readlane(mrow, jj);
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(Q) + r * pitch4, (short)0,
+                                             (int)((recbytes + 3u) & ~3u), 0x00020000);
+  };
+  struct Row {
+    uint4 w;
+    uint32_t s;
+  };
+  auto ldr = [&](__amdgpu_buffer_rsrc_t rs, Row& v) __attribute__((always_inline)) {
+    const auto a = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0);
+    v.w = uint4{a[0], a[1], a[2], a[3]};
+    v.s = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)soff, 0, 0);
+  };
+  auto acc = [&](const Row& v) __attribute__((always_inline)) {
+    const float qe = __uint_as_float(v.s << 16), qs = __uint_as_float(v.s & 0xFFFF0000u);
+    QQ += f2v{qe, qs};
+    const f2v qe2{qe, qe}, qs2{qs, qs};
+    const uint32_t w[BCPL / 2] = {v.w.x, v.w.y, v.w.z, v.w.w};
+#pragma unroll
+    for (int q = 0; q < BCPL / 2; ++q) {
+      const f2v me{(float)(w[q] & 0xFFu), (float)((w[q] >> 16) & 0xFFu)};
+      const f2v ms{(float)((w[q] >> 8) & 0xFFu), (float)(w[q] >> 24)};
+      S[q] = __builtin_elementwise_fma(me, qe2, S[q]);
+      N[q] = __builtin_elementwise_fma(ms, qs2, N[q]);
+      if constexpr (NAIS_Q16_COLA) {
+        A[(2 * q) % QNA] = fmaf(fabsf(ms[0] - 128.f), qs, A[(2 * q) % QNA]);
+        A[(2 * q + 1) % QNA] = fmaf(fabsf(ms[1] - 128.f), qs, A[(2 * q + 1) % QNA]);
+      }
+    }
+  };
+  int jj = 0;
+  for (; jj + BGU8 <= jn; jj += BGU8) {
+    Row v[BGU8];
+#pragma unroll
+    for (int g = 0; g < BGU8; ++g) ldr(row(jj + g), v[g]);
+#pragma unroll
+    for (int g = 0; g < BGU8; ++g) acc(v[g]);
+  }
+  for (; jj < jn; ++jj) {
+    Row v;
+    ldr(row(jj), v);
+    acc(v);
+  }
+}
+
 __device__ __forceinline__ float sigmoid_ref(float l) { return 1.0f / (1.0f + expf(-l)); }
 __device__ __forceinline__ unsigned long long score_key(float sc, int64_t c) {
   return ((unsigned long long)ord_f32_p(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)c);
@@ -695,6 +764,71 @@ __device__ __forceinline__ float lthr_of(unsigned long long thr, float beta) {
   return (float)L;
 }
 
+// The interval from q16 sums (bound_rows_q16; DESIGN.md (d) "q16"). The format's contract per term,
+// e and p = e*s the tabled pair, q_e / q_s the scales of its group:
+//   (m_e - 2^-14) q_e <= e < (m_e + 1 + 2^-14) q_e,   (m_s - 2^-14) q_s <= p < (m_s + 1 + 2^-14) q_s
+// (2^-14: the quantiser's v_rcp_f32 and one fp32 rounding on a quotient below 256). With S^ = sum
+// m_e q_e, N^ = sum m_s q_s, Qe = sum q_e, Qs = sum q_s as the gather forms them in fp32 (exact
+// products; h additions each, within g / 2 of their sums; N^ = N' - 128 Qs from N' <= 255 Qs, so
+// N^ is within 200 g Qs of its real value), the tabled sums lie in
+//   Se in [S^ - 2^-13 Qe, S^ + (1 + 2^-13) Qe],   Ne in [N^ - 512 g Qs, N^ + (1 + 512 g) Qs]
+// (512 g >= 2^-11 also holds the 2^-14 slack and Qs's own rounding), and sum |p| <= A = 128 Qs
+// (1 + 2^-10), as |m_s| <= 128. From there as make_bounds, with these ends in place of the
+// truncation's [S^, S^ (1 + 2^-7)] and 2^-7 A^: the exact gather's fp32 sums satisfy
+//   Sa in [(S^ - 2^-13 Qe)(1 - 3g)(1 - eta), (S^ + (1 + 2^-13) Qe)(1 + 3g)(1 + eta) + tiny],
+//   Na in [N^ - 512 g Qs - r, N^ + (1 + 512 g) Qs + r],
+//   r = (4g + eta2) A + (S^ + (1 + 2^-13) Qe)(1 + 2^-7)(1 + eta) ds + tiny
+// (the 1 + 2^-7 on the ds term is kept as slack for Na's rounding on the widened terms). A lower
+// end of S at or below 0 (S^ = 0, or Qe swamping it) fails `ok`: refined whatever tau is, as do
+// non-finite scales (Qe or Qs not finite).
+struct QEnds {
+  float slo, shi, nlo, nhi;
+};
+__device__ __forceinline__ QEnds q16_ends(float S, float N, float Qe, float Qs, float Acol, int64_t hl,
+                                          const Widen& w) {
+  const float g = (float)hl * 0x1p-23f + 0x1p-20f;
+  const float tiny = (float)hl * 0x1p-126f;
+  const float A = NAIS_Q16_COLA ? (Acol + Qs) * (1.f + 0x1p-10f) : 128.f * (1.f + 0x1p-10f) * Qs;
+  const float su = S + (1.f + 0x1p-13f) * Qe;
+  QEnds q;
+  q.slo = (S - 0x1p-13f * Qe) * (1.f - 3.f * g) * (1.f - w.eta);
+  q.shi = su * (1.f + 3.f * g) * (1.f + w.eta) + tiny;
+  const float rn = (4.f * g + w.eta2) * A + (tiny + su * (1.f + 0x1p-7f) * (1.f + w.eta) * w.ds);
+  q.nlo = N - 512.f * g * Qs - rn;
+  q.nhi = N + (1.f + 512.f * g) * Qs + rn;
+  return q;
+}
+__device__ __forceinline__ Bounds make_bounds_q16(float S, float N, float Qe, float Qs, float Acol,
+                                                  int64_t hl, float beta, const Widen& w) {
+  const QEnds q = q16_ends(S, N, Qe, Qs, Acol, hl, w);
+  Bounds b;
+  b.slo = q.slo;
+  b.shi = q.shi;
+  b.nlo = q.nlo;
+  b.nhi = q.nhi;
+  if (beta == 0.5f) {
+    b.dlo = sqrtf(b.slo);
+    b.dhi = sqrtf(b.shi);
+  } else {
+    const float p0 = powf(b.slo, beta), p1 = powf(b.shi, beta);
+    b.dlo = fminf(p0, p1);
+    b.dhi = fmaxf(p0, p1);
+  }
+  b.ok = b.slo > 0.f && b.dlo > 0.f && __builtin_isfinite(b.dhi) && __builtin_isfinite(b.nlo) &&
+         __builtin_isfinite(b.nhi);
+  return b;
+}
+// may_reach for q16 sums: the same test on the same ends (a lower end of S <= 0 or NaN keeps the
+// candidate: v_sqrt / v_rcp give NaN or inf, and only l < L drops one).
+__device__ __forceinline__ bool may_reach_q16(float S, float N, float Qe, float Qs, float Acol, int64_t hl,
+                                              float L, const Widen& w) {
+  const QEnds q = q16_ends(S, N, Qe, Qs, Acol, hl, w);
+  const float sd = q.nhi >= 0.f ? q.slo : q.shi;
+  float l = q.nhi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(sd));
+  l += fabsf(l) * 0x1p-17f;
+  return !(l < L) || !(q.slo > 0.f);
+}
+
 // Sorts the wave's LDS keys L[0 .. n) descending (bitonic over the next power of two >= 64,
 // padded with 0 keys; L must have room for it).
 __device__ void wave_sort_desc(unsigned long long* L, int n) {
@@ -747,15 +881,22 @@ __device__ int wave_merge_keys(unsigned long long* L, int cnt, const unsigned lo
   return n < k ? n : k;
 }
 
-__global__ void __launch_bounds__(GW * 64)
-pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_t* __restrict__ rowmap,
-                       const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
-                       const int32_t* __restrict__ users, int32_t nusers, int64_t col0, int64_t cols,
-                       float beta, int k, unsigned long long* __restrict__ lokeys,
-                       int32_t* __restrict__ locount, unsigned long long* __restrict__ surv,
-                       int32_t* __restrict__ scount, int cap, const int32_t* __restrict__ erows,
-                       const int64_t* __restrict__ spans, int32_t* __restrict__ work,
-                       const float* __restrict__ widen) {
+// The bounded gather's body, shared by its two table formats. Q16 = false: the hi words (HI, row
+// pitch ld words). Q16 = true: the q16 block (HI = its base, ld = its row pitch in 4-byte words,
+// qpairs = the byte offset of a row's pair words, qx0 = the launch's first column within the
+// block); the sums and the score interval differ (bound_rows_q16, make_bounds_q16), the lists, the
+// survivors, the compaction, the overflow mark and the work queue are the same code.
+template <bool Q16>
+__device__ __forceinline__ void
+pair_bound_topk_body(const uint32_t* __restrict__ HI, int64_t ld, uint32_t qpairs, uint32_t qx0,
+                     const int32_t* __restrict__ rowmap,
+                     const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
+                     const int32_t* __restrict__ users, int32_t nusers, int64_t col0, int64_t cols,
+                     float beta, int k, unsigned long long* __restrict__ lokeys,
+                     int32_t* __restrict__ locount, unsigned long long* __restrict__ surv,
+                     int32_t* __restrict__ scount, int cap, const int32_t* __restrict__ erows,
+                     const int64_t* __restrict__ spans, int32_t* __restrict__ work,
+                     const float* __restrict__ widen) {
   __shared__ unsigned long long lk[GW][BK_LDS];
   __shared__ uint32_t hm[GW][BSTRIPE / 32];   // history POIs of this block, one bit per column
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -796,11 +937,12 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
   if (lane < BSTRIPE / 32) hm[w][lane] = 0u;
   wave_lds_sync();
   f2v S2[BCPL / 2], N2[BCPL / 2];
-  float A[BCPL];
+  float A[Q16 ? QNA : BCPL];   // Q16: no per-column A (128 Qs bounds it)
+  f2v QQ{0.f, 0.f};          // Q16: (Qe, Qs) = the sums of the lane's group scales
 #pragma unroll
   for (int q = 0; q < BCPL / 2; ++q) S2[q] = N2[q] = f2v{0.f, 0.f};
 #pragma unroll
-  for (int q = 0; q < BCPL; ++q) A[q] = 0.f;
+  for (int q = 0; q < (Q16 ? QNA : BCPL); ++q) A[q] = 0.f;
   for (int64_t j0 = 0; j0 < hl; j0 += 64) {
     const int jn = __builtin_amdgcn_readfirstlane((int)std::min<int64_t>(64, hl - j0));
     int32_t mrow = 0;
@@ -812,7 +954,11 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
       const int64_t r = c - col0;
       if (r >= 0 && r < cols) atomicOr(&hm[w][r >> 5], 1u << (r & 31));
     }
-    bound_rows(HI, ld, mrow, jn, (uint32_t)(cols * 4), (uint32_t)(x * 4), S2, N2, A);
+    if constexpr (Q16)
+      bound_rows_q16(HI, ld, mrow, jn, qpairs + 2u * (qx0 + (uint32_t)cols), qpairs + 2u * (qx0 + (uint32_t)x),
+                     4u * ((qx0 >> 4) + (uint32_t)(lane >> 1)), S2, N2, QQ, reinterpret_cast<float (&)[QNA]>(A));
+    else
+      bound_rows(HI, ld, mrow, jn, (uint32_t)(cols * 4), (uint32_t)(x * 4), S2, N2, A);
   }
   wave_lds_sync();
   float S[BCPL], N[BCPL];
@@ -820,6 +966,7 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
   for (int q = 0; q < BCPL; ++q) {
     S[q] = S2[q / 2][q & 1];
     N[q] = N2[q / 2][q & 1];
+    if constexpr (Q16) N[q] = fmaf(-128.f, QQ[1], N[q]);   // sum (m_s + 128) q_s -> N^ = sum m_s q_s
   }
   const unsigned long long thr = cnt == k ? lk_last : 0ull;   // valid keys are > 0
   // upper keys of every candidate; lower keys only where the upper one reaches thr (else neither
@@ -841,9 +988,11 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
       if (hl == 0) {   // exact: logit 0 -> 0.5 for every candidate
         live |= 1u << q;
         ho[q] = lo_[q] = ord_f32_p(0.5f);
-      } else if (may_reach(S[q], N[q], A[q], hl, Lthr, wd)) {
+      } else if (Q16 ? may_reach_q16(S[q], N[q], QQ[0], QQ[1], A[Q16 ? q % QNA : 0], hl, Lthr, wd)
+                     : may_reach(S[q], N[q], A[Q16 ? 0 : q], hl, Lthr, wd)) {
         live |= 1u << q;
-        const Bounds b = make_bounds(S[q], N[q], A[q], hl, beta, wd);
+        const Bounds b = Q16 ? make_bounds_q16(S[q], N[q], QQ[0], QQ[1], A[Q16 ? q % QNA : 0], hl, beta, wd)
+                             : make_bounds(S[q], N[q], A[Q16 ? 0 : q], hl, beta, wd);
         ho[q] = b.ok ? ord_f32_p(upper_score(b)) : 0xFFFFFFFFu;
         if (b.ok && key_of(ho[q], q) > thr) lo_[q] = ord_f32_p(lower_score(b));
       }
@@ -905,6 +1054,35 @@ pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_
   }
   wave_lds_sync();   // the next slot's hm / lk writers after this slot's readers
   }
+}
+
+__global__ void __launch_bounds__(GW * 64)
+pair_bound_topk_kernel(const uint32_t* __restrict__ HI, int64_t ld, const int32_t* __restrict__ rowmap,
+                       const int64_t* __restrict__ indptr, const int64_t* __restrict__ indices,
+                       const int32_t* __restrict__ users, int32_t nusers, int64_t col0, int64_t cols,
+                       float beta, int k, unsigned long long* __restrict__ lokeys,
+                       int32_t* __restrict__ locount, unsigned long long* __restrict__ surv,
+                       int32_t* __restrict__ scount, int cap, const int32_t* __restrict__ erows,
+                       const int64_t* __restrict__ spans, int32_t* __restrict__ work,
+                       const float* __restrict__ widen) {
+  pair_bound_topk_body<false>(HI, ld, 0u, 0u, rowmap, indptr, indices, users, nusers, col0, cols, beta, k,
+                              lokeys, locount, surv, scount, cap, erows, spans, work, widen);
+}
+
+// The same gather from a q16 block (include/nais.h): Q = the block, pitch4 = its row pitch in
+// 4-byte words, qpairs = 4 * ceil(ld / 16), qx0 = the stripe's first column within the block.
+// 4 waves per SIMD asked for (128 VGPRs; 129 without), as the hi-word kernel runs.
+__global__ void __launch_bounds__(GW * 64, NAIS_Q16_WAVES)
+pair_bound_topk_q16_kernel(const uint32_t* __restrict__ Q, int64_t pitch4, uint32_t qpairs, uint32_t qx0,
+                           const int32_t* __restrict__ rowmap, const int64_t* __restrict__ indptr,
+                           const int64_t* __restrict__ indices, const int32_t* __restrict__ users,
+                           int32_t nusers, int64_t col0, int64_t cols, float beta, int k,
+                           unsigned long long* __restrict__ lokeys, int32_t* __restrict__ locount,
+                           unsigned long long* __restrict__ surv, int32_t* __restrict__ scount, int cap,
+                           const int32_t* __restrict__ erows, const int64_t* __restrict__ spans,
+                           int32_t* __restrict__ work, const float* __restrict__ widen) {
+  pair_bound_topk_body<true>(Q, pitch4, qpairs, qx0, rowmap, indptr, indices, users, nusers, col0, cols,
+                             beta, k, lokeys, locount, surv, scount, cap, erows, spans, work, widen);
 }
 
 // Phase 2: per user, the exact scores of the candidates whose upper key reaches the final tau (all
@@ -1589,6 +1767,48 @@ int32_t nais_pair_bound_topk_widened(const uint32_t* hi, int64_t ld, const int32
                        reinterpret_cast<unsigned long long*>(surv), surv_count, (int)surv_cap, entry_rows,
                        spans, work, widen);
     const int32_t rc = nais_internal_check_launch("pair_bound_topk_kernel");
+    if (rc) return rc;
+  }
+  return NAIS_OK;
+}
+
+int64_t nais_q16_pitch(int64_t ld) {
+  return ld <= 0 ? 0 : (4 * ((ld + 15) / 16) + 2 * ld + 127) / 128 * 128;
+}
+
+int32_t nais_pair_bound_topk_q16(const void* q16, int64_t ld, int64_t pitch, const int32_t* rowmap,
+                                 const int64_t* indptr, const int64_t* indices, const int32_t* users,
+                                 int32_t num_users, int64_t col0, int64_t cols, float beta, int32_t k,
+                                 uint64_t* lo_keys, int32_t* lo_count, uint64_t* surv,
+                                 int32_t* surv_count, int32_t surv_cap, const int32_t* entry_rows,
+                                 const int64_t* spans, const float* widen, int32_t* work, void* stream) {
+  if (num_users < 0 || col0 < 0 || cols < 0 || ld < cols || k <= 0 || surv_cap < 64)
+    return nais_internal_fail(NAIS_E_INVALID, "bad shape");
+  if (k > BK_LDS - 256) return nais_internal_fail(NAIS_E_UNSUPPORTED, "k must be <= 256");
+  if (col0 + cols > 0xFFFFFFFFll) return nais_internal_fail(NAIS_E_UNSUPPORTED, "POI ids must fit 32 bits");
+  if (num_users == 0 || cols == 0) return NAIS_OK;
+  if (!q16 || !rowmap || !indptr || !indices || !users || !lo_keys || !lo_count || !surv || !surv_count)
+    return nais_internal_fail(NAIS_E_INVALID, "missing pointer");
+  if (ld > (1 << 24) || pitch != nais_q16_pitch(ld) || (reinterpret_cast<uintptr_t>(q16) & 15) != 0)
+    return nais_internal_fail(NAIS_E_INVALID, "pitch must be nais_q16_pitch(ld) and q16 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  unsigned groups = (unsigned)((num_users + GW - 1) / GW);
+  if (work) {   // as nais_pair_bound_topk_widened
+    const int ncu = nais_internal_stream_cus(st);
+    if (ncu <= 0) return nais_internal_fail(NAIS_E_HIP, "device attributes");
+    groups = std::min<unsigned>(groups, (unsigned)ncu * 5u);
+  }
+  const uint32_t qpairs = (uint32_t)(4 * ((ld + 15) / 16));
+  for (int64_t s0 = 0; s0 < cols; s0 += BSTRIPE) {   // one launch per stripe: one writer per list
+    if (work && hipMemsetAsync(work, 0, sizeof(int32_t), st) != hipSuccess)
+      return nais_internal_fail(NAIS_E_HIP, "hipMemsetAsync(work)");
+    hipLaunchKernelGGL(pair_bound_topk_q16_kernel, dim3(groups), dim3(GW * 64), 0, st,
+                       reinterpret_cast<const uint32_t*>(q16), pitch / 4, qpairs, (uint32_t)s0, rowmap,
+                       indptr, indices, users, num_users, col0 + s0, std::min<int64_t>(BSTRIPE, cols - s0),
+                       beta, (int)k, reinterpret_cast<unsigned long long*>(lo_keys), lo_count,
+                       reinterpret_cast<unsigned long long*>(surv), surv_count, (int)surv_cap, entry_rows,
+                       spans, work, widen);
+    const int32_t rc = nais_internal_check_launch("pair_bound_topk_q16_kernel");
     if (rc) return rc;
   }
   return NAIS_OK;
