@@ -305,6 +305,19 @@ X1Q_GATHER_MARGIN = 1.34
 # puts the three-term fit (at 2.25 bytes) there. One job on one device size, as above.
 X1Q16_RATE = 5.7e14
 X1Q16_GATHER_MARGIN = 1.16
+# The q16 route after the cut of its VALU work (profiles/lean, DESIGN.md (d) "Less VALU work in the
+# q16 route"): the table's chains start from S*b1 as the first MFMA's srcC (no copies), the gather
+# merges a few offered keys by rank and takes its pruning threshold in fp32. Fitted on config 4 as
+# above: the tables cost 35.2 CU-s where they bound the step (232.5 / 227.5 / 222.9 / 219.8 ms busy
+# on 154 / 156 / 158 / 160 CUs), 5.96e14 FLOP/s on the whole chip; the gathers run 196.6 / 199.0 /
+# 201.9 / 204.4 ms busy on 102 / 100 / 98 / 96 CUs and 212.6 on 94 (below three whole XCDs), 0.93
+# of what they took before, so the margin is 1.16 * 0.93. The step is lowest at 160 / 96 in three
+# alternating rounds (268.2-269.0 ms; 162: 269.7-269.8, 158: 270.7-271.0, 156: 274.8-275.7, 154:
+# 279.2-280.1): the tables still set it there, and the gather's floor of three XCDs keeps the
+# split from moving their way. `auto_table_cus(..., lean=True)` uses these and that floor; the
+# default keeps the two values above.
+X1Q16L_RATE = 5.96e14
+X1Q16L_GATHER_MARGIN = 1.08
 # Bounded gather + exact refine (round 6; include/nais.h nais_pair_bound_topk): the fused top-k
 # from split16 tables -- the gather streams only their hi halves (4 bytes per history entry and
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
@@ -463,7 +476,8 @@ def _ondemand_shape(model, prm):
 
 
 def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, work_queues=True,
-                   gather_bytes=8, k=None, users=None, products=None, table_queue=False, q16=False):
+                   gather_bytes=8, k=None, users=None, products=None, table_queue=False, q16=False,
+                   lean=False):
     """CUs for the table stream (the rest gather), in steps of ncu / 8 (counts off a multiple of 32
     leave a shader engine short and lose -- DESIGN.md, CU split), from a cost model fitted
     on config 4 and config 5 (profiles/r1/cfg5p/, re-fitted in round 3 on the fp16x6 tables:
@@ -489,6 +503,11 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     `q16` with `products=1` and `table_queue`: the ring holds q16 blocks (ABI 20): 2.25 gathered
     bytes per pair, the table at the rate its quantising tail leaves it (X1Q16_RATE) and the
     gather margin fitted on the q16 sweep (X1Q16_GATHER_MARGIN). Ignored on every other route.
+
+    `lean` with `q16`: the table kernel without its accumulator-start copies and the gather with
+    its merge by rank and fp32 threshold (profiles/lean): the table rate and gather margin fitted
+    on that sweep (X1Q16L_RATE, X1Q16L_GATHER_MARGIN), and at least three whole XCDs left to the
+    gather. False (the default) keeps every value this function gave before. Ignored on every other route.
 
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
@@ -530,8 +549,9 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     if x1q:
         t_tab = J * NC * 2.0 * H * din_k / X1Q_RATE
     q16 = bool(q16) and x1q
+    lean = bool(lean) and q16
     if q16:
-        t_tab = J * NC * 2.0 * H * din_k / X1Q16_RATE
+        t_tab = J * NC * 2.0 * H * din_k / (X1Q16L_RATE if lean else X1Q16_RATE)
         gbytes = entries * NC * 2.25
     if x6n and dist:
         # the distance K-step: 2 v_mfma_f32_16x16x1_4b_f32 (32 cycles each) per PAIR of 16-hidden
@@ -567,10 +587,12 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
         if q16:
             if users and k:
                 per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k, 2.25)
-            per_cu /= X1Q16_GATHER_MARGIN
+            per_cu /= X1Q16L_GATHER_MARGIN if lean else X1Q16_GATHER_MARGIN
     cap = 7.5e12   # the memory side's rate for the gather, chip-wide
     best, best_t = ncu // 2, None
     for n in range((ncu // 4 + step - 1) // step * step, ncu - step + 1, step):
+        if lean and ncu - n < 3 * xcd:
+            break   # the q16 gather breaks off below three whole XCDs (profiles/q16: 268 ms on 88 CUs)
         g_pen = 1.0
         if gather_bytes == 4 and PAIR_CU_LAYOUT == "contiguous" and (ncu - 1) // xcd - n // xcd + 1 <= 2:
             # a bounded gather confined to two XCDs (contiguous CU ids) costs ~4 % more CU-time per
@@ -930,7 +952,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                                         J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
                                         users=m, products=ond_products if ondm[0] else None,
-                                        table_queue=ondm[0], q16=q16[0])
+                                        table_queue=ondm[0], q16=q16[0], lean=q16[0])
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
             # the on-demand route runs its streams as queues on the engine grid too: config 4 at
             # 160 table CUs ran level with 162 as a queue, 393.3 ms on the fixed grid against

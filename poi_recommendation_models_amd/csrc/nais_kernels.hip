@@ -683,6 +683,28 @@ struct Epi16<HB, false> {          // b1 / w2 read from LDS: acc starts at 0, un
   }
 };
 
+// Epi16<HB, true> with S*b1 held as one 16-register tuple per hidden block (the ONE instances): the
+// first MFMA of an item's chain takes the tuple as srcC and writes the item's accumulators, so no
+// copy of S*b1 into them precedes the chain (16 v_mov_b64 per item and wave at HB = 2). The tuple
+// stays live across items, which keeps the compiler from tying it to the destination. Same sums,
+// same bits: the chain still starts from S*b1.
+template <int HB>
+struct Epi16V {
+  floatx16 bsv[HB];
+  float ws[HB * 16];
+  __device__ __forceinline__ void rescale(const float* Eimg, int hh, float S, float invS) {
+#pragma unroll
+    for (int i = 0; i < HB * 16; ++i) {
+      bsv[i / 16][i % 16] = Eimg[hh * HB * 16 + i] * S;
+      ws[i] = Eimg[2 * HB * 16 + hh * HB * 16 + i] * invS;
+    }
+  }
+  __device__ __forceinline__ float init(int i) const { return bsv[i / 16][i % 16]; }
+  __device__ __forceinline__ float term(int i, float acc, float) const {
+    return ws[i] * relu_bits(acc);
+  }
+};
+
 template <int HB>
 struct Epi16L {                    // per-wave LDS copy of S*b1 and w2/S (S wave-uniform): acc starts at S*b1
   const float* pb;
@@ -1011,6 +1033,8 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   static_assert(!ONE || (NPC == 2 && PIPE && !DIST),
                 "one-product logits: the pipelined fp16x3 shapes, no distance inputs");
   static_assert(!Q16 || ONE, "q16 words: the one-product bound table only");
+  static_assert(!ONE || C::WLDS || C::EREGS,
+                "one-product logits take Epi16V in place of Epi16<HB, true> only: b1 / w2 pre-scaled in VGPRs");
   // s = h_j . t_c for the chunk's 32 items on the matrix pipe (one 32x32 tile per wave and chunk,
   // the same split-fp16 3-product scheme) instead of a 2*DH-term VALU dot per item and lane
   constexpr bool SMF = JCB == 32;
@@ -1154,7 +1178,8 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   float S = 0.f, N = 0.f;
   bool in_hist = false;
   // b1 / w2 pre-scaled in VGPRs when pipelined; read from LDS (unscaled, one fma per use) when wide
-  std::conditional_t<C::WLDS, Epi16L<HB>, Epi16<HB, C::EREGS>> epi;
+  // (the ONE instances: the same values with S*b1 as the first MFMA's srcC tuple, Epi16V)
+  std::conditional_t<C::WLDS, Epi16L<HB>, std::conditional_t<ONE, Epi16V<HB>, Epi16<HB, C::EREGS>>> epi;
 
   // build the fragments of chunk-local item jj into ring slot (grp, it)
   // build the fragments of chunk-local item jj into ring slot (grp, it); wv is pre-scaled by S_A
@@ -1253,7 +1278,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     const int pj = live ? prev : 0;
     const float* hr = hrows + pj * D + hh * DH;
     float sd = 0.f, ap = 0.f;
-    if (MMA) {
+    if (MMA && !ONE) {   // ONE: the chain's first MFMA reads S*b1 as srcC instead (Epi16V)
 #pragma unroll
       for (int hb = 0; hb < HB; ++hb)
 #pragma unroll
@@ -1270,8 +1295,12 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
             const uint4 u4 = src[q * NE + (hb * KS + s) * 64 + lane];
             ap_[q] = *reinterpret_cast<const half8*>(&u4);
           }
-          if constexpr (ONE) accN[hb] = mfma16(ap_[0], tb[s][0], accN[hb]);
-          else accN[hb] = mfma_pieces<NPC>(ap_, tb[s], accN[hb]);
+          if constexpr (ONE) {
+            if (s == 0) accN[hb] = mfma16(ap_[0], tb[0][0], epi.bsv[hb]);
+            else accN[hb] = mfma16(ap_[0], tb[s][0], accN[hb]);
+          } else {
+            accN[hb] = mfma_pieces<NPC>(ap_, tb[s], accN[hb]);
+          }
         }
       }
       if constexpr (EPIL) {

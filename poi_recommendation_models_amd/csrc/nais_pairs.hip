@@ -754,14 +754,40 @@ __device__ __forceinline__ bool may_reach(float S, float N, float A, int64_t hl,
 // L for may_reach from the k-th key's score ts: upper_score(l) <= sigmoid_fp32(l) (1 + 2^-20) <
 // ts for every l < L = logit(ts (1 - 2^-18)) less a margin (ts = 1.0f: L ~ 12.5, below which the
 // upper score is < 1.0f). -inf when there is no such bound (list not full, ts <= 0, NaN, beta).
+//
+// In fp32 on v_rcp_f32 / v_log_f32 (thr comes from a load, so a double-precision log and division
+// would run on the vector unit once per visit), kept at or below the double-precision value
+//   Ld = log(p / (1 - p)) - 1e-6 (1 + |log(p / (1 - p))|),  p = ts (1 - 2^-18),
+// rounded to fp32, which the margin above was derived for. The accuracies taken for v_rcp_f32 and
+// v_log_f32 below are the ISA manual's documented 1 ulp, not figures measured on a device; the
+// headroom at the end is there for that. With u = 2^-24:
+//   pn = ts - ts 2^-18 (one fma): within u of p, relatively;
+//   qn = (1 - ts) + ts 2^-18: 1 - ts is exact for ts >= 0.5 (Sterbenz) and within u otherwise,
+//        the fma rounds once more: within 2u of 1 - p. It is never below 2^-18, so 1 - p does not
+//        cancel as 1 - fl(p) would at ts near 1;
+//   r = pn * v_rcp(qn): v_rcp_f32 is good to 1 ulp (2u), the product rounds once: r is within
+//        6.1u of p / (1 - p), |ln r - ln(p / (1 - p))| <= 3.7e-7;
+//   v_log_f32 is good to 1 ulp of log2 r; taken as 2 ulp, and as 2^-22 absolute where |log2 r| < 1:
+//        <= 2^-22 max(1, |log2 r|), in ln units <= 2^-22 (ln 2 + |ln r|) <= 2.4e-7 (1 + |L|);
+//   the - 64 of a scaled ts and the scaling by ln 2 round once each: 2u |L|.
+// Together below 7.5e-7 (1 + |L|). The fp32 value of Ld may lie u |Ld| below Ld, and the margin
+// is itself formed and subtracted in fp32 (2u |L|): the margin 3e-6 (1 + |L|) holds 1e-6 + 7.5e-7
+// + 1.8e-7 = 1.93e-6 and leaves 1e-6 (1 + |L|) over, room for a v_log_f32 four times coarser
+// still. It costs 2e-6 (1 + |L|) of pruning depth, well inside the 2^-17 |l| that may_reach
+// already allows. ts below 2^-64 (denormals too, which v_log_f32 would flush) is scaled by 2^64
+// first; qn is then 1.
 __device__ __forceinline__ float lthr_of(unsigned long long thr, float beta) {
   if (thr == 0ull || beta != 0.5f) return -__builtin_inff();
   const float ts = unord_f32_p((uint32_t)(thr >> 32));
   if (!(ts > 0.f && ts <= 1.f)) return -__builtin_inff();
-  const double p = (double)ts * (1.0 - 0x1p-18);
-  double L = log(p / (1.0 - p));
-  L -= 1e-6 * (1.0 + fabs(L));
-  return (float)L;
+  const bool small = ts < 0x1p-64f;
+  const float tx = small ? ts * 0x1p64f : ts;
+  const float pn = __builtin_fmaf(tx, -0x1p-18f, tx);
+  const float qn = __builtin_fmaf(ts, 0x1p-18f, 1.f - ts);
+  const float r = pn * __builtin_amdgcn_rcpf(qn);
+  const float l2 = __builtin_amdgcn_logf(r) - (small ? 64.f : 0.f);
+  const float L = l2 * 0.693147180559945f;
+  return L - 3e-6f * (1.f + fabsf(L));
 }
 
 // The interval from q16 sums (bound_rows_q16; DESIGN.md (d) "q16"). The format's contract per term,
@@ -878,6 +904,65 @@ __device__ int wave_merge_keys(unsigned long long* L, int cnt, const unsigned lo
     if ((offer >> q) & 1u) L[pos++] = kq[q];
   const int n = cnt + m;
   wave_sort_desc(L, n);
+  return n < k ? n : k;
+}
+
+// The same merge for a few offered keys, by rank instead of a sort of the whole list: O[0 .. m),
+// m <= MERGE_INS, are the offered keys (wave-uniform, any order, the rest of O zero) and L[0 .. cnt)
+// the descending list. All keys differ (a key carries its column), so the merged order is
+// determined: a list entry moves down by the number of offered keys above it, an offered key lands
+// at (list entries above it) + (offered keys above it). Every entry is read before any is written,
+// and what falls at or behind k is dropped, so L[0 .. min(cnt + m, k)) is what wave_sort_desc
+// leaves there. cnt <= 256 (four entries per lane).
+#ifndef NAIS_MERGE_INS
+#define NAIS_MERGE_INS 8   // most keys a visit may offer for the merge by rank; 0: always the sort (4 / 8 / 16 A/B: profiles/lean)
+#endif
+constexpr int MERGE_INS = NAIS_MERGE_INS;
+__device__ __forceinline__ int wave_insert_keys(unsigned long long* L, int cnt,
+                                                const unsigned long long (&O)[MERGE_INS > 0 ? MERGE_INS : 1],
+                                                int m, int k) {
+  constexpr int NI = MERGE_INS > 0 ? MERGE_INS : 1;
+  const int lane = threadIdx.x & 63;
+  unsigned long long v[4];
+  int up[4];          // offered keys above this lane's entry t
+  int above[NI];      // list entries above offered key j (wave-uniform)
+#pragma unroll
+  for (int j = 0; j < NI; ++j) above[j] = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = lane + 64 * t;
+    v[t] = 0ull;
+    up[t] = 0;
+    if (64 * t < cnt) {   // wave-uniform
+      const bool in = i < cnt;
+      v[t] = in ? L[i] : 0ull;
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const unsigned long long gt = __ballot(v[t] > O[j]);   // a zero v (not in the list) is above nothing
+        above[j] += __popcll(gt);
+        up[t] += (in && !(v[t] > O[j])) ? 1 : 0;               // O[j] = 0 (not offered) is above nothing
+      }
+    }
+  }
+  unsigned long long mine = 0ull;
+  int pos = 0;
+#pragma unroll
+  for (int j = 0; j < NI; ++j)
+    if (lane == j) {
+      mine = O[j];
+      pos = above[j];
+    }
+#pragma unroll
+  for (int j = 0; j < NI; ++j) pos += O[j] > mine ? 1 : 0;
+  wave_lds_sync();
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int i = lane + 64 * t;
+    if (i < cnt && i + up[t] < k) L[i + up[t]] = v[t];
+  }
+  if (lane < m && pos < k) L[pos] = mine;
+  wave_lds_sync();
+  const int n = cnt + m;
   return n < k ? n : k;
 }
 
@@ -999,17 +1084,43 @@ pair_bound_topk_body(const uint32_t* __restrict__ HI, int64_t ld, uint32_t qpair
       if (lo_[q] != 0u && key_of(lo_[q], q) > thr) offer |= 1u << q;
     }
   }
-  // the list of lower bounds: two merges of <= 256 offered keys (the LDS holds k + 256)
+  // the list of lower bounds: up to MERGE_INS offered keys go in by rank, more by two sorting
+  // merges of <= 256 offered keys each (the LDS holds k + 256)
   unsigned long long* L = lk[w];
   int nk = cnt;
   const bool merged = __ballot(offer != 0u) != 0ull;
   if (merged) {
     for (int i = lane; i < cnt; i += 64) L[i] = lokeys[slot * k + i];
-    wave_lds_sync();
-    const unsigned long long l0[4] = {key_of(lo_[0], 0), key_of(lo_[1], 1), key_of(lo_[2], 2), key_of(lo_[3], 3)};
-    const unsigned long long l1[4] = {key_of(lo_[4], 4), key_of(lo_[5], 5), key_of(lo_[6], 6), key_of(lo_[7], 7)};
-    nk = wave_merge_keys<4>(L, nk, l0, offer & 0xFu, k);
-    nk = wave_merge_keys<4>(L, nk, l1, offer >> 4, k);
+    // the keys offered per column, counted on the scalar unit: after a user's first blocks a visit
+    // offers a few keys to a sorted list of k, which go in by rank (wave_insert_keys); more of
+    // them (the first block offers every column) take the sort
+    unsigned long long ob[BCPL];
+    int m = 0;
+#pragma unroll
+    for (int q = 0; q < BCPL; ++q) {
+      ob[q] = __ballot((offer >> q) & 1u);
+      m += __popcll(ob[q]);
+    }
+    if (MERGE_INS > 0 && m <= MERGE_INS) {
+      const int cu = __builtin_amdgcn_readfirstlane(cnt);
+      int base = cu;   // the offered keys staged behind the list, in column-then-lane order
+#pragma unroll
+      for (int q = 0; q < BCPL; ++q) {
+        if ((offer >> q) & 1u) L[base + __popcll(ob[q] & ((1ull << lane) - 1ull))] = key_of(lo_[q], q);
+        base += __popcll(ob[q]);
+      }
+      wave_lds_sync();
+      unsigned long long O[MERGE_INS > 0 ? MERGE_INS : 1];
+#pragma unroll
+      for (int j = 0; j < (MERGE_INS > 0 ? MERGE_INS : 1); ++j) O[j] = j < m ? L[cu + j] : 0ull;
+      nk = wave_insert_keys(L, cu, O, m, k);
+    } else {
+      wave_lds_sync();
+      const unsigned long long l0[4] = {key_of(lo_[0], 0), key_of(lo_[1], 1), key_of(lo_[2], 2), key_of(lo_[3], 3)};
+      const unsigned long long l1[4] = {key_of(lo_[4], 4), key_of(lo_[5], 5), key_of(lo_[6], 6), key_of(lo_[7], 7)};
+      nk = wave_merge_keys<4>(L, nk, l0, offer & 0xFu, k);
+      nk = wave_merge_keys<4>(L, nk, l1, offer >> 4, k);
+    }
     for (int i = lane; i < nk; i += 64) lokeys[slot * k + i] = L[i];
     if (lane == 0) locount[slot] = nk;
   }
