@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 20   /* 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 21   /* 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -739,6 +739,108 @@ int32_t nais_geoie_train_step(const nais_geoie_params_t* params, int64_t user, c
 int32_t nais_sgd(float* param, const float* grad, int64_t rows, int32_t dim, float lr,
                  float weight_decay, const int32_t* stamp, int32_t tag, int64_t skip_row,
                  const int32_t* err, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BPR (model.py:587-620; DESIGN.md "BPR"): matrix factorisation, score(u, c) = embed_user[u] .
+ * embed_item[c] in fp32. Both kernels below form that dot product as ONE fmaf chain over
+ * e = 0, 1, ..., D - 1 from +0 (the scorer on v_mfma_f32_32x32x2_f32, which is that chain), fold
+ * -0 into +0 and report every NaN as the quiet NaN 0x7FC00000, so the same (u, c) has the same
+ * bits from both.
+ *
+ *   nais_bpr_forward     out_i[t] = score(user[t], item_i[t]), out_j[t] = score(user[t], item_j[t])
+ *                        for t < n: model.py:613-618. item_j / out_j may both be NULL (the
+ *                        evaluation calls the model with item_i == item_j, validation.py:144).
+ *                        Bad shapes and pointers return NAIS_E_*; ids are device data, so a row
+ *                        whose user or item id is outside the tables reads nothing and is NaN.
+ *   nais_bpr_score_topk  replaces the user loop of validation.py:138-147: for users[num_users]
+ *                        (int32 ids) and the CSR (indptr, indices; rows ascending) the k <= 256
+ *                        best candidates of [0, P) \ history(u), as keys in the format of
+ *                        nais_pair_gather_topk: ordered(score) << 32 | (0xFFFFFFFF - poi), sorted
+ *                        descending in keys[slot*k ...] with kcount[slot] of them valid (NaN first,
+ *                        ties by ascending POI id; a user with an empty history has all P
+ *                        candidates). nais_topk_keys_finish turns them into ids and scores. No
+ *                        score is written to memory: each user keeps the key of its k-th best
+ *                        (tau) and only candidates that beat it are kept -- one float compare
+ *                        per score, then the whole key for the few that pass. Survivors are
+ *                        looked up in the history when the user's buffer is compacted, not
+ *                        before they are buffered; tau is taken after that, so a history POI
+ *                        never sets it.
+ *                        num_chunks: column chunks the catalog is split into (0: chosen from the
+ *                        shape); the keys do not depend on it. workspace: of
+ *                        nais_bpr_score_topk_workspace_size(params, num_users, k, num_chunks) bytes
+ *                        (0 for one chunk; may then be NULL).
+ * embed_dim 1..256, num_pois < 2^24 (NAIS_E_UNSUPPORTED otherwise).
+ */
+typedef struct nais_bpr_params {
+  int32_t embed_dim;            /* D, 1..256                                                  */
+  int64_t num_users;            /* rows of embed_user                                         */
+  int64_t num_pois;             /* P = rows of embed_item                                     */
+  const float* embed_user;      /* embed_user.weight [num_users, D]   model.py:596            */
+  const float* embed_item;      /* embed_item.weight [P, D]           model.py:597            */
+} nais_bpr_params_t;
+
+int32_t nais_bpr_forward(const nais_bpr_params_t* params, const int64_t* user,
+                         const int64_t* item_i, const int64_t* item_j, int64_t n, float* out_i,
+                         float* out_j, void* stream);
+size_t nais_bpr_score_topk_workspace_size(const nais_bpr_params_t* params, int32_t num_users,
+                                          int32_t k, int32_t num_chunks);
+int32_t nais_bpr_score_topk(const nais_bpr_params_t* params, const int64_t* indptr,
+                            const int64_t* indices, const int32_t* users, int32_t num_users,
+                            int32_t k, int32_t num_chunks, uint64_t* keys, int32_t* kcount,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BPR training (run.py:490-509, batches.py:6-22; DESIGN.md "BPR"). A batch is n triples
+ * (user[t], item_i[t], item_j[t]): a positive and a negative POI of one user. With U = embed_user,
+ * I = embed_item, all in fp32:
+ *   x_t = U[u_t] . I[i_t] - U[u_t] . I[j_t];  s_t = sigmoid(x_t);  L = -sum_t log s_t   (run.py:506)
+ *   g_t = (-1 / s_t) * ((1 - s_t) * s_t)   -- in that order, the composed form autograd produces
+ *         (log, then sigmoid): where s_t rounds to 0 the loss is inf and g_t is NaN, as the
+ *         reference's; it is NOT -(1 - s_t)
+ *   dU[u_t] += g_t (I[i_t] - I[j_t]);  dI[i_t] += g_t U[u_t];  dI[j_t] -= g_t U[u_t]
+ *   from the pre-step tables; users and items repeat across triples and every repeat is summed
+ *   before the row's one update p -= lr (grad + weight_decay p) (torch.optim.SGD, no momentum,
+ *   run.py:481-482). With weight_decay == 0 an untouched row stays bit-identical; otherwise every
+ *   element of both tables moves, the untouched rows by nais_sgd's dense pass.
+ *
+ *   nais_bpr_make_train_batch  get_BPR_batch (batches.py:6-22) on the device for users[num_users]
+ *       (int64 ids into a CSR of num_rows users; an id outside sets *err |= 2): user u with h
+ *       history POIs gives h triples at user / item_i / item_j
+ *       [offsets[slot] ...] (offsets: the caller's exclusive prefix sum of the h's): the positives
+ *       in CSR order, the negatives h distinct POIs drawn uniformly without replacement from
+ *       outside the history (the sampler of nais_make_train_batch, seeded per user from `seed`).
+ *       h > P - h sets *err to 1 and writes nothing for that user (the reference's negative[i]
+ *       raises there, batches.py:14-16). Triples come out grouped by user: the reference's final
+ *       random.shuffle(batch) (batches.py:17) only changes the order in which the step sums them.
+ *   nais_bpr_train_step  replaces run.py:504-509 for one batch, in place on both tables of
+ *       `params` (written through for this call). *loss_sum += L. Optional outputs: pred_i /
+ *       pred_j [n] (the two dots), g [n], grads (dense [num_users, D] / [P, D], zeroed by the
+ *       caller; only touched rows are written). stamp_user [num_users] / stamp_item [P]: int32,
+ *       zero-initialised once, `tag` a value no earlier step used; they mark the touched rows. An
+ *       id outside its table sets *err |= 2, and while *err is non-zero no table is written.
+ *       Deterministic: no float atomics. item_order [2n] int64 is a STABLE sort permutation of the
+ *       2n ids item_i[0..n) ++ item_j[0..n) (entry x < n is item_i[x], else item_j[x - n]);
+ *       user_order [n] the same for user[] (NULL: user[] is already grouped, as
+ *       nais_bpr_make_train_batch emits it). One wave per run of equal ids sums the run in that
+ *       order, so equal inputs give equal bits. Entries outside [0, 2n) / [0, n) are skipped.
+ */
+typedef struct nais_bpr_train_grads {
+  float* embed_user;            /* [num_users, D] dense dU, caller-zeroed                      */
+  float* embed_item;            /* [P, D]         dense dI, caller-zeroed                      */
+} nais_bpr_train_grads_t;
+
+int32_t nais_bpr_make_train_batch(const int64_t* indptr, const int64_t* indices,
+                                  int64_t num_rows, const int64_t* users, const int64_t* offsets, int64_t num_users,
+                                  int64_t num_pois, uint64_t seed, int64_t* user, int64_t* item_i,
+                                  int64_t* item_j, int32_t* err, void* stream);
+size_t nais_bpr_train_step_workspace_size(const nais_bpr_params_t* params, int64_t n);
+int32_t nais_bpr_train_step(const nais_bpr_params_t* params, const int64_t* user,
+                            const int64_t* item_i, const int64_t* item_j, int64_t n,
+                            const int64_t* user_order, const int64_t* item_order, float lr,
+                            float weight_decay, int32_t* stamp_user, int32_t* stamp_item,
+                            int32_t tag, float* loss_sum, int32_t* err, float* pred_i,
+                            float* pred_j, float* g, const nais_bpr_train_grads_t* grads,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step of NAIS_basic on one get_NAIS_batch batch (batches.py:24-50):

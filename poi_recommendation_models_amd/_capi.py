@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -39,7 +39,21 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_q16_pitch", "nais_pair_table_bound1_q16_queued", "nais_pair_bound_topk_q16",
            "nais_geoie_table", "nais_geoie_score", "nais_geoie_forward",
            "nais_geoie_make_train_batch", "nais_geoie_train_step_workspace_size",
-           "nais_geoie_train_step", "nais_sgd")
+           "nais_geoie_train_step", "nais_sgd", "nais_bpr_forward",
+           "nais_bpr_score_topk_workspace_size", "nais_bpr_score_topk", "nais_bpr_make_train_batch",
+           "nais_bpr_train_step_workspace_size", "nais_bpr_train_step")
+
+
+class NaisBPRParams(ctypes.Structure):
+    """Mirror of `nais_bpr_params_t` (include/nais.h)."""
+    _fields_ = [("embed_dim", ctypes.c_int32), ("num_users", ctypes.c_int64),
+                ("num_pois", ctypes.c_int64), ("embed_user", ctypes.c_void_p),
+                ("embed_item", ctypes.c_void_p)]
+
+
+class NaisBPRTrainGrads(ctypes.Structure):
+    """Mirror of `nais_bpr_train_grads_t` (include/nais.h)."""
+    _fields_ = [("embed_user", ctypes.c_void_p), ("embed_item", ctypes.c_void_p)]
 
 
 class NaisGeoIEParams(ctypes.Structure):
@@ -298,6 +312,21 @@ def load(path: str | None = None):
                                           ctypes.POINTER(NaisGeoIETrainGrads), vp, sz, vp]
     lib.nais_sgd.restype = i32
     lib.nais_sgd.argtypes = [vp, vp, i64, i32, f32, f32, vp, i32, i64, vp, vp]
+    lib.nais_bpr_forward.restype = i32
+    lib.nais_bpr_forward.argtypes = [ctypes.POINTER(NaisBPRParams), vp, vp, vp, i64, vp, vp, vp]
+    lib.nais_bpr_score_topk_workspace_size.restype = sz
+    lib.nais_bpr_score_topk_workspace_size.argtypes = [ctypes.POINTER(NaisBPRParams), i32, i32, i32]
+    lib.nais_bpr_score_topk.restype = i32
+    lib.nais_bpr_score_topk.argtypes = [ctypes.POINTER(NaisBPRParams), vp, vp, vp, i32, i32, i32, vp,
+                                        vp, vp, sz, vp]
+    lib.nais_bpr_make_train_batch.restype = i32
+    lib.nais_bpr_make_train_batch.argtypes = [vp, vp, i64, vp, vp, i64, i64, u64, vp, vp, vp, vp, vp]
+    lib.nais_bpr_train_step_workspace_size.restype = sz
+    lib.nais_bpr_train_step_workspace_size.argtypes = [ctypes.POINTER(NaisBPRParams), i64]
+    lib.nais_bpr_train_step.restype = i32
+    lib.nais_bpr_train_step.argtypes = [ctypes.POINTER(NaisBPRParams), vp, vp, vp, i64, vp, vp, f32,
+                                        f32, vp, vp, i32, vp, vp, vp, vp, vp,
+                                        ctypes.POINTER(NaisBPRTrainGrads), vp, sz, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

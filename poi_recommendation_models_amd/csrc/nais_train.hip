@@ -39,6 +39,7 @@
 #include "nais.h"
 #include "nais_internal.h"
 #include "nais_gx.h"
+#include "nais_sampler.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
@@ -71,15 +72,6 @@ __device__ __forceinline__ int crow(int blk, int r, int hh) {
 __device__ __forceinline__ int kdim(int s, int hh) { return crow(s >> 4, s & 15, hh); }
 // first of the 4 consecutive dims of K-steps 4g..4g+3
 __device__ __forceinline__ int kdim4(int g, int hh) { return 32 * (g >> 2) + 8 * (g & 3) + 4 * hh; }
-
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
 
 // Dropout as in nn.Dropout(p) (model.py:22): keep with probability 1-p and scale by 1/(1-p).
 // The draw for hidden unit i of pair (c, j) is a hash of (seed, c*n+j, i) -- same bits in every
@@ -738,38 +730,9 @@ __global__ void step_adagrad_dense_kernel(float* p, float* st, float* g, int64_t
 // user's positives in a random order, rows [pos_i, neg_i1 .. neg_i,ng], labels 1 / 0. Negatives
 // are the first n*ng members, in a pseudo-random order of [0, P), that are not positives: a
 // uniformly random distinct subset of the complement, as the reference's shuffle-and-slice --
-// the same distribution, not Python's `random` stream. The orders come from a seeded Feistel
-// permutation of [0, 4^h) walked down to [0, m) (cycle walking), so no sort is needed.
+// the same distribution, not Python's `random` stream. The orders come from the seeded Feistel
+// permutation of nais_sampler.h (cycle walking), so no sort is needed.
 // ---------------------------------------------------------------------------------------------
-// 8-round Feistel network on [0, 2^(2*hb)) keyed by the seed (round function: murmur finaliser;
-// 8 rounds: 4 leave a visible bias on domains of a few elements)
-__device__ __forceinline__ uint32_t feistel(uint32_t x, int hb, uint32_t s) {
-  const uint32_t mh = (1u << hb) - 1u;
-  uint32_t L = x >> hb, R = x & mh;
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const uint32_t f = mix32(R ^ (s + uint32_t(r) * 0x9e3779b9u)) & mh;
-    const uint32_t t = L ^ f;
-    L = R;
-    R = t;
-  }
-  return (L << hb) | R;
-}
-
-// bijection of [0, m): the Feistel permutation of [0, 2^(2 hb)) >= m, walked until it lands < m
-__device__ __forceinline__ uint32_t permute(uint32_t i, uint32_t m, int hb, uint32_t s) {
-  do {
-    i = feistel(i, hb, s);
-  } while (i >= m);
-  return i;
-}
-
-// half the bits of the smallest power of two >= m (m >= 2), rounded up
-__device__ __forceinline__ int half_bits(uint32_t m) {
-  const int k = 32 - __clz(m - 1);
-  return (k + 1) >> 1;
-}
-
 constexpr int BATCH_THREADS = 1024;
 
 __global__ void __launch_bounds__(BATCH_THREADS)

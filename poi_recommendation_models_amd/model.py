@@ -1102,3 +1102,103 @@ class GeoIE(nn.Module):
             print(t1)
             print(t2)
         return torch.sum(loss)
+
+
+class _BPRForward(torch.autograd.Function):
+    """BPR.forward under grad mode: `nais_bpr_forward` for the two predictions; the backward is
+    plain torch ops (index_add_ into dense gradients, as nn.Embedding's), so run.py:504-509 trains
+    unchanged. The fused step is `trainer.BPRTrainer`."""
+
+    @staticmethod
+    def forward(ctx, module, user, item_i, item_j, embed_user, embed_item):
+        pi, pj = module._run_forward(user, item_i, item_j)
+        ctx.save_for_backward(user, item_i, item_j, embed_user, embed_item)
+        return pi, pj
+
+    @staticmethod
+    def backward(ctx, gi, gj):
+        user, item_i, item_j, eu, ei = ctx.saved_tensors
+        user, item_i, item_j = user.reshape(-1), item_i.reshape(-1), item_j.reshape(-1)   # any shape
+        u, ri, rj = eu[user], ei[item_i], ei[item_j]
+        gi, gj = gi.reshape(-1, 1), gj.reshape(-1, 1)
+        du = torch.zeros_like(eu).index_add_(0, user, gi * ri + gj * rj)
+        di = torch.zeros_like(ei).index_add_(0, item_i, gi * u).index_add_(0, item_j, gj * u)
+        return None, None, None, None, du, di
+
+
+class BPR(nn.Module):
+    """BPR (model.py:587-620): `BPR(user_num, item_num, factor_num)`, the reference's parameter
+    and state_dict names (`embed_user.weight`, `embed_item.weight`), N(0, 0.01) init.
+
+    `forward(user, item_i, item_j) -> (prediction_i, prediction_j)` is the HIP kernel
+    `nais_bpr_forward` (under grad mode wrapped in an autograd Function whose backward is torch's
+    index_add_). The full-catalog evaluation is `bpr.score_topk` / `validation.BPR_validation`, the
+    fused training step `trainer.BPRTrainer`. Off the ROCm device it raises.
+
+    Every forward checks its ids against the tables and raises IndexError, as nn.Embedding
+    would (the kernel alone returns NaN for such a row). That check reads one flag back, a host
+    sync per call, so the unchanged `train_BPR` loop syncs once per batch here -- as it already
+    does on `loss.item()`; `BPRTrainer` and `bpr.score_topk` do not go through it."""
+
+    def __init__(self, user_num, item_num, factor_num):
+        super().__init__()
+        self.embed_user = nn.Embedding(user_num, factor_num)
+        self.embed_item = nn.Embedding(item_num, factor_num)
+        nn.init.normal_(self.embed_user.weight, std=0.01)      # model.py:600-601
+        nn.init.normal_(self.embed_item.weight, std=0.01)
+        self.user_num, self.POI_count, self.factor_num = user_num, item_num, factor_num
+
+    def _check_device(self, *tensors):
+        dev = self.embed_user.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"BPR: the model runs only on a ROCm device (parameters are on {dev}); "
+                               "move it with .to('cuda')")
+        for t in tensors:
+            if t is not None and t.device != dev:
+                raise RuntimeError(f"BPR: input on {t.device}, parameters on {dev}")
+        for n, p in self.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"BPR: parameter {n} must be contiguous float32")
+        return dev
+
+    def bpr_params(self) -> _capi.NaisBPRParams:
+        """`nais_bpr_params_t` view of this module's parameters (device pointers, no copies)."""
+        q = _capi.NaisBPRParams()
+        q.embed_dim = int(self.embed_user.weight.shape[1])
+        q.num_users = int(self.embed_user.weight.shape[0])
+        q.num_pois = int(self.embed_item.weight.shape[0])
+        q.embed_user = self.embed_user.weight.data_ptr()
+        q.embed_item = self.embed_item.weight.data_ptr()
+        return q
+
+    def _run_forward(self, user, item_i, item_j):
+        dev = self._check_device(user, item_i, item_j)
+        shape = user.shape
+        if item_i.shape != shape or item_j.shape != shape:
+            raise ValueError(f"user, item_i and item_j must have one shape; got {tuple(shape)}, "
+                             f"{tuple(item_i.shape)}, {tuple(item_j.shape)}")
+        same = item_j is item_i
+        u = user.reshape(-1).to(torch.int64).contiguous()
+        i = item_i.reshape(-1).to(torch.int64).contiguous()
+        j = None if same else item_j.reshape(-1).to(torch.int64).contiguous()
+        n = u.numel()
+        if n:   # nn.Embedding raises on an id outside its table; the kernel would return NaN
+            bad = (u < 0) | (u >= self.embed_user.weight.shape[0]) | (i < 0) | (i >= self.POI_count)
+            if j is not None:
+                bad |= (j < 0) | (j >= self.POI_count)
+            if bool(bad.any()):
+                raise IndexError("BPR: user or item id out of range")
+        oi = torch.empty(n, dtype=torch.float32, device=dev)
+        oj = None if same else torch.empty(n, dtype=torch.float32, device=dev)
+        _capi.check(_capi.load().nais_bpr_forward(
+            self.bpr_params(), u.data_ptr(), i.data_ptr(), _capi.ptr(j), n, oi.data_ptr(),
+            _capi.ptr(oj), _capi.stream_handle(dev)), "nais_bpr_forward")
+        oi = oi.reshape(shape)
+        return oi, (oi if same else oj.reshape(shape))
+
+    def forward(self, user, item_i, item_j):                   # model.py:603-620
+        if torch.is_grad_enabled() and (self.embed_user.weight.requires_grad or
+                                        self.embed_item.weight.requires_grad):
+            return _BPRForward.apply(self, user, item_i, item_j, self.embed_user.weight,
+                                     self.embed_item.weight)
+        return self._run_forward(user, item_i, item_j)

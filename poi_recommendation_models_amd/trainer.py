@@ -27,6 +27,10 @@ shared history, num_ng distinct uniform negatives per positive), not Python's ra
 `GeoIETrainer` is the same treatment of train_GeoIE (run.py:687-715): `nais_geoie_make_train_batch`
 is get_GeoIE_batch (batches.py:204-242) on the device and `nais_geoie_train_step` is forward,
 loss_function, backward and torch.optim.SGD in place on the four embedding tables.
+
+`BPRTrainer` is train_BPR's loop (run.py:490-509): `nais_bpr_make_train_batch` is get_BPR_batch
+(batches.py:6-22) for a whole list of users and `nais_bpr_train_step` is forward, the BPR loss,
+backward and torch.optim.SGD in place on both tables, deterministic (no float atomics).
 """
 from __future__ import annotations
 
@@ -419,4 +423,137 @@ class GeoIETrainer:
         if bad:
             self.bad_rows.zero_()
             warnings.warn(f"GeoIE: {bad} row(s) with a non-finite loss term (model.py:820)", RuntimeWarning)
+        return float(self.loss_sum.item())
+
+
+class BPRTrainer:
+    """train_BPR's loop (run.py:490-509) on the device: `batch()` is get_BPR_batch
+    (batches.py:6-22) for a list of users, `step()` is run.py:504-509 (forward, the loss
+    -sum(log(sigmoid(pred_i - pred_j))), backward, torch.optim.SGD(lr, weight_decay) without
+    momentum) updating both embedding tables in place, `epoch()` the loop with one host sync at
+    its end. A step is deterministic: the same batch from the same state gives the same bits."""
+
+    def __init__(self, model, train_matrix, lr=0.01, weight_decay=0.0):
+        from .model import BPR
+        if not isinstance(model, BPR):
+            raise NotImplementedError(f"BPRTrainer: {type(model).__name__} is not BPR")
+        dev = model._check_device()
+        self.model, self.dev = model, dev
+        self.csr = device_csr(train_matrix, dev)
+        if self.csr.shape[1] != model.POI_count or self.csr.shape[0] > model.user_num:
+            raise ValueError(f"train_matrix is {self.csr.shape}, model has {model.user_num} users "
+                             f"and {model.POI_count} POIs")
+        self.lr, self.weight_decay = float(lr), float(weight_decay)
+        self.step_count = 0
+        self._st_u = torch.zeros(model.user_num, dtype=torch.int32, device=dev)
+        self._st_i = torch.zeros(model.POI_count, dtype=torch.int32, device=dev)
+        self.loss_sum = torch.zeros(1, device=dev)
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ws = torch.empty(0, dtype=torch.uint8, device=dev)
+
+    def batch(self, user_ids, seed=None):
+        """get_BPR_batch(train_matrix, P, user_ids) on the device: (user, item_i, item_j), int64
+        [n] each, n = the users' history lengths summed. Per user the positives in CSR order and
+        as many distinct negatives drawn uniformly from outside the history; triples are grouped
+        by user (the reference's final shuffle only changes the summation order). A user with
+        more positives than POIs outside its history raises ValueError (the reference's
+        negative[i] raises IndexError there)."""
+        users = np.asarray(list(user_ids) if not isinstance(user_ids, np.ndarray) else user_ids,
+                           dtype=np.int64).reshape(-1)
+        if len(users) and (users.min() < 0 or users.max() >= self.csr.shape[0]):
+            raise IndexError("BPRTrainer.batch: user id out of range")
+        hl = self.csr.hist_len[users] if len(users) else np.zeros(0, np.int64)
+        P = self.csr.shape[1]
+        if np.any(hl > P - hl):
+            u = int(users[np.argmax(hl > P - hl)])
+            raise ValueError(f"user {u}: {int(self.csr.hist_len[u])} positives exceed the "
+                             f"{P - int(self.csr.hist_len[u])} POIs outside the history "
+                             "(get_BPR_batch cannot draw them)")
+        off = np.zeros(len(users), dtype=np.int64)
+        if len(users):
+            off[1:] = np.cumsum(hl)[:-1]
+        n = int(hl.sum())
+        d = self.dev
+        user = torch.empty(n, dtype=torch.int64, device=d)
+        item_i = torch.empty(n, dtype=torch.int64, device=d)
+        item_j = torch.empty(n, dtype=torch.int64, device=d)
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        if n:
+            users_d, off_d = torch.from_numpy(users).to(d), torch.from_numpy(off).to(d)   # both alive
+            _capi.check(_capi.load().nais_bpr_make_train_batch(
+                self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(), self.csr.shape[0], users_d.data_ptr(),
+                off_d.data_ptr(), len(users), P, seed, user.data_ptr(), item_i.data_ptr(), item_j.data_ptr(),
+                self._err.data_ptr(), _capi.stream_handle(d)), "nais_bpr_make_train_batch")
+        return user, item_i, item_j
+
+    def step(self, user, item_i, item_j, pred=None, grads=None):
+        """One fused step (run.py:504-509) on n triples, in any order (batch()'s, or the
+        reference's shuffled get_BPR_batch). `pred`: optional dict that receives prediction_i /
+        prediction_j / g ([n] f32 each); `grads`: optional dict that receives the dense gradients
+        under the parameter names (embed_user.weight [U, D], embed_item.weight [P, D])."""
+        m = self.model
+        dev = m._check_device(user, item_i, item_j)
+        user = user.reshape(-1).to(torch.int64).contiguous()
+        item_i = item_i.reshape(-1).to(torch.int64).contiguous()
+        item_j = item_j.reshape(-1).to(torch.int64).contiguous()
+        n = user.numel()
+        if item_i.numel() != n or item_j.numel() != n or n == 0:
+            raise ValueError(f"user, item_i and item_j must hold the same n >= 1 triples; got "
+                             f"{n}, {item_i.numel()}, {item_j.numel()}")
+        # the stable orders the step sums in (plumbing; the sums themselves are the kernels')
+        uorder = torch.sort(user, stable=True)[1]
+        iorder = torch.sort(torch.cat([item_i, item_j]), stable=True)[1]
+        gs = _capi.NaisBPRTrainGrads()
+        if grads is not None:
+            gu = torch.zeros_like(m.embed_user.weight)
+            gi = torch.zeros_like(m.embed_item.weight)
+            grads.update({"embed_user.weight": gu, "embed_item.weight": gi})
+            gs.embed_user, gs.embed_item = gu.data_ptr(), gi.data_ptr()
+        pi = pj = g = None
+        if pred is not None:
+            pi, pj, g = (torch.empty(n, device=dev) for _ in range(3))
+            pred.update({"prediction_i": pi, "prediction_j": pj, "g": g})
+        lib = _capi.load()
+        prm = m.bpr_params()
+        need = lib.nais_bpr_train_step_workspace_size(prm, n)
+        if self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=dev)
+        self.step_count += 1
+        _capi.check(lib.nais_bpr_train_step(
+            prm, user.data_ptr(), item_i.data_ptr(), item_j.data_ptr(), n, uorder.data_ptr(),
+            iorder.data_ptr(), self.lr, self.weight_decay, self._st_u.data_ptr(),
+            self._st_i.data_ptr(), self.step_count, self.loss_sum.data_ptr(), self._err.data_ptr(),
+            _capi.ptr(pi), _capi.ptr(pj), _capi.ptr(g), gs if grads is not None else None,
+            self._ws.data_ptr(), self._ws.numel(), _capi.stream_handle(dev)), "nais_bpr_train_step")
+        self._bump_versions()
+
+    def _bump_versions(self):
+        """As NAISTrainer._bump_versions: the step writes through raw pointers."""
+        for q in self.model.parameters():
+            increment_version(q)
+
+    def epoch(self, batch_size=4096, shuffle=True):
+        """run.py:490-509: the users (shuffled as run.py:490-491) in batches of `batch_size`, one
+        batch() and one step() each. Returns the epoch's loss (run.py:507's `lo`), read with the
+        epoch's one host sync."""
+        users = np.arange(self.csr.shape[0], dtype=np.int64)
+        if shuffle:
+            users = users[torch.randperm(len(users)).numpy()]
+        self.model.train()
+        self.loss_sum.zero_()
+        for b0 in range(0, len(users), int(batch_size)):
+            u, i, j = self.batch(users[b0:b0 + int(batch_size)])
+            if u.numel():
+                self.step(u, i, j)
+        return self.finish()
+
+    def finish(self):
+        """Host sync: the accumulated loss. Raises if a step saw an id outside its table or a
+        batch could not be drawn (that step and every later one left the tables untouched)."""
+        err = int(self._err.item())
+        if err:
+            self._err.zero_()
+            raise RuntimeError(f"BPRTrainer: an id outside its table or an undrawable batch (code {err}); "
+                               "that step and the later ones were not applied")
         return float(self.loss_sum.item())

@@ -136,6 +136,23 @@ def GeoIE_validation(model, args, num_users, test_positive, val_positive, train_
     return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
 
 
+def BPR_validation(model, args, num_users, test_positive, val_positive, train_matrix, k_list):
+    """validation.py:133-153 (BPR): per user the args.topk best POIs outside its training history
+    by embed_user[u] . embed_item[c], scored and selected in one fused kernel (`bpr.score_topk`;
+    no score row is written). A user with fewer than args.topk candidates raises RuntimeError, as
+    the reference's torch.topk does. Single-process only: there is no distributed BPR
+    evaluation."""
+    import numpy as np
+    from .bpr import score_topk as bpr_topk
+    from .catalog import device_csr
+    model.eval()                                               # validation.py:134
+    csr = device_csr(train_matrix, model._check_device())
+    if np.any(csr.shape[1] - csr.hist_len[:num_users] < args.topk):
+        raise RuntimeError("selected index k out of range")   # torch.topk's error
+    ids, _ = bpr_topk(model, csr, range(num_users), args.topk)
+    return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
+
+
 def new4_validation(model, args, num_users, test_positive, val_positive, train_matrix,
                     businessRegionEmbedList, k_list, nearPOI, distributed=None):
     """validation.py:254-280 (New4): the context tables are built once (the reference rebuilds
