@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "nais_geo.h"
+#include "nais_geo_cr.h"
 #include "nais_internal.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -94,6 +95,33 @@ __device__ __forceinline__ double clamp_dist(double d) {   // run.py:44, as nais
   return (100.0 < lo) ? 100.0 : lo;
 }
 
+// make_geo / ref_dist of nais_geo.h (the same operations in the same order) with the sin, cos and
+// acos of nais_geo_cr.h: the batch's distances feed the model as the reference's dist_mat does,
+// and between POIs closer than 0.3 km a last-bit difference moves them by up to a hundred
+// float32 ulps. The products and sums are plain operators with contraction switched off:
+// __dmul_rn / __dadd_rn are inline x * y and x + y of a header compiled with contraction on,
+// which the compiler fuses (cosv's last product into its sum) wherever they are inlined.
+__device__ __forceinline__ Geo make_geo_cr(double lat, double lng) {
+  NAIS_CR_NO_CONTRACT
+  const double phi = (90.0 - lat) * kD2R;
+  nais_geo_cr::DD s, c;
+  if (fabs(phi) < 1e5) {
+    nais_geo_cr::sincos_dd(phi, &s, &c, 3);
+  } else {
+    s.h = sin(phi);
+    c.h = cos(phi);
+  }
+  return Geo{lat, lng, s.h, c.h, lng * kD2R};
+}
+
+__device__ __forceinline__ double ref_dist_cr(const Geo& p1, const Geo& p2) {
+  NAIS_CR_NO_CONTRACT
+  if (fabs(p1.lat - p2.lat) < 1e-6 && fabs(p1.lng - p2.lng) < 1e-6) return 0.0;
+  const double t = (p1.sphi * p2.sphi) * nais_geo_cr::cr_cos(p1.theta - p2.theta);
+  const double cosv = t + p1.cphi * p2.cphi;
+  return nais_geo_cr::cr_acos(cosv) * 6371.0;
+}
+
 __device__ __forceinline__ float sigmoidf(float s) { return 1.0f / (1.0f + expf(-s)); }
 
 // torch.optim.SGD without momentum: g' = g + weight_decay * p; p -= lr * g'
@@ -120,7 +148,7 @@ __global__ __launch_bounds__(256) void geoie_batch_fill_kernel(
     int64_t t = target[i];
     if (t < 0 || t >= P) t = 0;   // only after an h mismatch (*err is set): keep the reads in range
     Lt[tid] = t;
-    if (coords) Lg[tid] = make_geo(coords[2 * t], coords[2 * t + 1]);
+    if (coords) Lg[tid] = make_geo_cr(coords[2 * t], coords[2 * t + 1]);
     // freq is attached by CSR position, not by POI (batches.py:238-239)
     if (ct == 0) freq[i] = int64_t(data[indptr[user] + i / (1 + ng)]);
   }
@@ -131,9 +159,9 @@ __global__ __launch_bounds__(256) void geoie_batch_fill_kernel(
   if (hj < 0 || hj >= P) hj = 0;
   const int nr = (b - r0 < GT_BR) ? int(b - r0) : GT_BR;
   if (coords) {
-    const Geo gh = make_geo(coords[2 * hj], coords[2 * hj + 1]);
+    const Geo gh = make_geo_cr(coords[2 * hj], coords[2 * hj + 1]);
     for (int i = 0; i < nr; ++i)   // dist_mat[target][hist] = dist(coo[target], coo[hist]), run.py:44
-      dist[(r0 + i) * ld + j] = float(clamp_dist(ref_dist(Lg[i], gh)));
+      dist[(r0 + i) * ld + j] = float(clamp_dist(ref_dist_cr(Lg[i], gh)));
   } else {
     for (int i = 0; i < nr; ++i) dist[(r0 + i) * ld + j] = float(dist_mat[Lt[i] * P + hj]);
   }
