@@ -318,6 +318,19 @@ X1Q16_GATHER_MARGIN = 1.16
 # default keeps the two values above.
 X1Q16L_RATE = 5.96e14
 X1Q16L_GATHER_MARGIN = 1.08
+# The q16 route with the |z| epilogue in the table kernel (profiles/absepi, DESIGN.md (d) "The |z|
+# epilogue"; the padded D = 64, 32 < H <= 64 instances, the ones that keep the s tile). Fitted on
+# config 4 as above: the tables run 214.3 / 212.7 / 211.7 / 209.4 ms busy on 154 / 156 / 158 / 160
+# CUs (33.0-33.5 CU-s), 6.26e14 FLOP/s on the whole chip from the 160-CU runs; the gathers beside
+# the shorter tables run 201.9 / 204.7 / 208.1 / 211.2 ms busy on 102 / 100 / 98 / 96 CUs and 218.0
+# on 94 (below three whole XCDs): the margin 1.07 is the one at which the three-term fit gives the
+# 211.2 ms at 96 CUs (1.00-1.07 give 160, 1.08 gives 158). The step is lowest at 160 / 96 or level
+# with it (three alternating rounds: 260.4-261.1 ms; 158: 260.9-261.6, 156: 261.0-261.4, 154:
+# 261.9-263.0, 162: 266.0-266.2): the streams are within 2 ms of each other there, and the gather's
+# floor of three XCDs bars the table stream from more. `auto_table_cus(..., lean=True,
+# absepi=True)` uses these; without the keyword every value is what it was.
+X1Q16A_RATE = 6.26e14
+X1Q16A_GATHER_MARGIN = 1.07
 # Bounded gather + exact refine (round 6; include/nais.h nais_pair_bound_topk): the fused top-k
 # from split16 tables -- the gather streams only their hi halves (4 bytes per history entry and
 # candidate instead of 8), keeps per user the k best LOWER bounds of the exact scores and the
@@ -477,7 +490,7 @@ def _ondemand_shape(model, prm):
 
 def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, work_queues=True,
                    gather_bytes=8, k=None, users=None, products=None, table_queue=False, q16=False,
-                   lean=False):
+                   lean=False, absepi=False):
     """CUs for the table stream (the rest gather), in steps of ncu / 8 (counts off a multiple of 32
     leave a shader engine short and lose -- DESIGN.md, CU split), from a cost model fitted
     on config 4 and config 5 (profiles/r1/cfg5p/, re-fitted in round 3 on the fp16x6 tables:
@@ -508,6 +521,11 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
     its merge by rank and fp32 threshold (profiles/lean): the table rate and gather margin fitted
     on that sweep (X1Q16L_RATE, X1Q16L_GATHER_MARGIN), and at least three whole XCDs left to the
     gather. False (the default) keeps every value this function gave before. Ignored on every other route.
+
+    `absepi` with `lean`: the table kernel's |z| epilogue (profiles/absepi), which the padded
+    D = 64, 32 < H <= 64 instances take: the table rate and gather margin fitted on that sweep
+    (X1Q16A_RATE, X1Q16A_GATHER_MARGIN), the same floor of three XCDs. False (the default) keeps
+    every value this function gave before. Ignored on every other route and shape.
 
     `work_queues`: whether this job's table AND gather launches take the work counter (the x6n
     table kernel of the NAIS modules and the fused top-k gather). Only then may the
@@ -550,8 +568,9 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
         t_tab = J * NC * 2.0 * H * din_k / X1Q_RATE
     q16 = bool(q16) and x1q
     lean = bool(lean) and q16
+    absepi = bool(absepi) and lean and D == 64 and 32 < H <= 64
     if q16:
-        t_tab = J * NC * 2.0 * H * din_k / (X1Q16L_RATE if lean else X1Q16_RATE)
+        t_tab = J * NC * 2.0 * H * din_k / (X1Q16A_RATE if absepi else X1Q16L_RATE if lean else X1Q16_RATE)
         gbytes = entries * NC * 2.25
     if x6n and dist:
         # the distance K-step: 2 v_mfma_f32_16x16x1_4b_f32 (32 cycles each) per PAIR of 16-hidden
@@ -587,7 +606,8 @@ def auto_table_cus(model, J, NC, entries, ncu, prior=False, block_bytes=None, wo
         if q16:
             if users and k:
                 per_cu = gbytes / bounded_gather_cu_seconds(entries, NC, users, k, 2.25)
-            per_cu /= X1Q16L_GATHER_MARGIN if lean else X1Q16_GATHER_MARGIN
+            per_cu /= (X1Q16A_GATHER_MARGIN if absepi else X1Q16L_GATHER_MARGIN if lean
+                       else X1Q16_GATHER_MARGIN)
     cap = 7.5e12   # the memory side's rate for the gather, chip-wide
     best, best_t = ncu // 2, None
     for n in range((ncu // 4 + step - 1) // step * step, ncu - step + 1, step):
@@ -952,7 +972,7 @@ def _score_topk_pairs(model, train_matrix, users, k, region_of, coords, latlon_m
                                         J * ld * (4 if ondm[0] else 8),   # a block: hi words alone
                                         work_queues=wq_both, gather_bytes=4 if bnd[0] else 8, k=k,
                                         users=m, products=ond_products if ondm[0] else None,
-                                        table_queue=ondm[0], q16=q16[0], lean=q16[0])
+                                        table_queue=ondm[0], q16=q16[0], lean=q16[0], absepi=q16[0])
                          if PAIR_TABLE_CUS < 0 else PAIR_TABLE_CUS)
             # the on-demand route runs its streams as queues on the engine grid too: config 4 at
             # 160 table CUs ran level with 162 as a queue, 393.3 ms on the fixed grid against

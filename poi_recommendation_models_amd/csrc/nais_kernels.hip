@@ -688,20 +688,27 @@ struct Epi16<HB, false> {          // b1 / w2 read from LDS: acc starts at 0, un
 // copy of S*b1 into them precedes the chain (16 v_mov_b64 per item and wave at HB = 2). The tuple
 // stays live across items, which keeps the compiler from tying it to the destination. Same sums,
 // same bits: the chain still starts from S*b1.
-template <int HB>
+// ABS: the |z| epilogue (catalog_score_x3b_kernel's ABSE): ws holds w2 / (2 S) -- the halving is a
+// power-of-two scaling, exact -- and a term is one v_fma_f32 with the |.| source modifier,
+// ap = fma(|acc|, ws, ap), in place of v_maximum3_f32 + v_fmac_f32. A NaN accumulator stays a NaN.
+template <int HB, bool ABS = false>
 struct Epi16V {
   floatx16 bsv[HB];
   float ws[HB * 16];
   __device__ __forceinline__ void rescale(const float* Eimg, int hh, float S, float invS) {
+    const float wsc = ABS ? 0.5f * invS : invS;
 #pragma unroll
     for (int i = 0; i < HB * 16; ++i) {
       bsv[i / 16][i % 16] = Eimg[hh * HB * 16 + i] * S;
-      ws[i] = Eimg[2 * HB * 16 + hh * HB * 16 + i] * invS;
+      ws[i] = Eimg[2 * HB * 16 + hh * HB * 16 + i] * wsc;
     }
   }
   __device__ __forceinline__ float init(int i) const { return bsv[i / 16][i % 16]; }
   __device__ __forceinline__ float term(int i, float acc, float) const {
     return ws[i] * relu_bits(acc);
+  }
+  __device__ __forceinline__ float abs_term(int i, float acc, float ap) const {
+    return __builtin_fmaf(__builtin_fabsf(acc), ws[i], ap);
   }
 };
 
@@ -999,8 +1006,14 @@ struct CfgB {
   // S*b1 and the epilogue is relu + fma (3 VALU per value instead of 4), no VGPRs spent
   static constexpr bool WLDS = PIPE && !EREGS;
   static constexpr int ESCL = WLDS ? NW * EPI : 0;
+  // ABSE: the |z| epilogue of the one-product form where it keeps the s tile (JCB = 32) and the LDS
+  // has the room (the kernel's comment): per wave the chunk's s tile and L tile, [32 items][32
+  // candidates] floats each, then v = W1^T w2 (D floats) and c0 = w2 . b1 (one float, padded)
+  static constexpr bool ABSE = NPA == 1 && NPC == 2 && PIPE && EREGS && !DIST && JCB == 32;
+  static constexpr int TILES = ABSE ? NW * 2 * 1024 + D + 16 : 0;
   static constexpr size_t REST = size_t(ADIST) * 4 + size_t(EPI) * 4 + size_t(ESCL) * 4 + 64 +
-                                 size_t(JCB) * D * 4 + size_t(JCB) * 4 + (DIST ? size_t(JCB) * 16 : 0);
+                                 size_t(JCB) * D * 4 + size_t(JCB) * 4 + (DIST ? size_t(JCB) * 16 : 0) +
+                                 size_t(TILES) * 4;
   static constexpr size_t BYTES = size_t(2) * G * IB + REST;
   static_assert(!PIPE || G % 2 == 0, "the pipelined steps alternate two accumulator sets per item");
 };
@@ -1038,6 +1051,18 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   // s = h_j . t_c for the chunk's 32 items on the matrix pipe (one 32x32 tile per wave and chunk,
   // the same split-fp16 3-product scheme) instead of a 2*DH-term VALU dot per item and lane
   constexpr bool SMF = JCB == 32;
+  // ABSE: the ONE instances that keep the s tile take the logit's w2 . relu(z) as
+  //   1/2 (sum_i w2_i z_i + sum_i w2_i |z_i|),
+  // the second sum from the one-product accumulators at one v_fma_f32 per value (Epi16V<HB, true>),
+  // the first, linear in x = h_j (.) t_c, as L(j, c) = v . x + c0 with v = W1^T w2 and c0 = w2 . b1:
+  // a second three-product 32 x 32 tile per wave and chunk with A rows v (.) h_j beside the s tile's
+  // h_j. Both tiles go unscaled to the wave's own LDS slot, rows = items, columns = candidates (a
+  // wave reads back what it wrote itself: no barrier), so the tail reads its pair's s and L / 2 + c0 / 2
+  // with two ds_read_b32 and the 16 tile registers are free during the item loop. The other ONE
+  // instances (JCB = 64: no s tile, the h . t dot on the VALU) keep the relu epilogue. DESIGN.md (d),
+  // "The |z| epilogue".
+  constexpr bool ABSE = ONE && C::ABSE;
+  static_assert(!C::ABSE || ONE, "the tiles' LDS is laid out for the one-product form alone");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint4* ring = reinterpret_cast<uint4*>(smem);       // [2 groups][G items][piece][NE]
   float* Adist = reinterpret_cast<float*>(ring + 2 * G * NPA * NE);
@@ -1047,6 +1072,8 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   float* hrows = red + 16;
   int32_t* hid = reinterpret_cast<int32_t*>(hrows + JCB * D);
   double* hco = reinterpret_cast<double*>(hid + JCB);
+  float* tiles = reinterpret_cast<float*>(hid + JCB);   // ABSE (no hco there): [wave][s | L][item][candidate]
+  float* vimg = tiles + NW * 2 * 1024;                  // ABSE: v[0, D), then c0
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hh = lane >> 5;
   int32_t* wi_sh = reinterpret_cast<int32_t*>(red + 15);   // block_max_n uses red[0, NW)
@@ -1078,6 +1105,20 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     const int hh2 = rem / (HB * 16), hr = rem % (HB * 16), hb = hr / 16, r = hr % 16;
     const int i = acc_row(hb, r, hh2);
     Eimg[f] = (i < p.H) ? (which == 0 ? p.b1[i] : p.w2[i]) : 0.f;
+  }
+  // ABSE: v_k = sum_i w2_i W1[i][k] by thread k < D and c0 = w2 . b1 by thread D, fp32 fma chains
+  // over i ascending (one order for every workgroup and launch form); Vmax = max |v| (a NaN dropped)
+  float Vmax = 0.f;
+  if constexpr (ABSE) {
+    float av = 0.f;
+    if (tid <= D) {
+      float t = 0.f;
+      for (int i = 0; i < p.H; ++i)
+        t = __builtin_fmaf(p.w2[i], tid < D ? p.w1[(int64_t)i * p.din + tid] : p.b1[i], t);
+      vimg[tid] = t;
+      if (tid < D) av = fabsf(t);
+    }
+    Vmax = block_max_n<NW>(av, red);   // its barriers publish vimg
   }
 
   DistW dw{0.f, 0.f, 0.f};
@@ -1179,7 +1220,7 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   bool in_hist = false;
   // b1 / w2 pre-scaled in VGPRs when pipelined; read from LDS (unscaled, one fma per use) when wide
   // (the ONE instances: the same values with S*b1 as the first MFMA's srcC tuple, Epi16V)
-  std::conditional_t<C::WLDS, Epi16L<HB>, std::conditional_t<ONE, Epi16V<HB>, Epi16<HB, C::EREGS>>> epi;
+  std::conditional_t<C::WLDS, Epi16L<HB>, std::conditional_t<ONE, Epi16V<HB, ABSE>, Epi16<HB, C::EREGS>>> epi;
 
   // build the fragments of chunk-local item jj into ring slot (grp, it)
   // build the fragments of chunk-local item jj into ring slot (grp, it); wv is pre-scaled by S_A
@@ -1232,9 +1273,13 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
   // sd): table-mode stores or the user's running sums
   auto tail = [&](int pj, float ap, float sd, bool live) {
     const float2 aph = lane_halves(ap);
-    const float a = aph.x + aph.y;
+    float a = aph.x + aph.y;
     float sv;
-    if (SMF) {   // item pj's row of the s tile: register ((pj/8)*4 + pj%4) of lane half (pj/4)%2
+    if constexpr (ABSE) {   // item pj's row of the wave's two tiles; both lane halves read the same words
+      const float* tp = tiles + wave * 2048 + pj * 32 + (lane & 31);
+      sv = tp[0];
+      a += tp[1024];        // (ap_lo + ap_hi) + (L / 2 + c0 / 2)
+    } else if (SMF) {   // item pj's row of the s tile: register ((pj/8)*4 + pj%4) of lane half (pj/4)%2
       const float2 sh2 = lane_halves(sacc[((pj >> 3) << 2) | (pj & 3)]);
       sv = (((pj >> 2) & 1) ? sh2.y : sh2.x) * invShSt;
     } else {
@@ -1305,8 +1350,10 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
       }
       if constexpr (EPIL) {
 #pragma unroll
-        for (int v = s * VPS; v < (s + 1) * VPS && v < NV; ++v)
-          ap += epi.term(v, accP[v / 16][v % 16], invS);
+        for (int v = s * VPS; v < (s + 1) * VPS && v < NV; ++v) {
+          if constexpr (ABSE) ap = epi.abs_term(v, accP[v / 16][v % 16], ap);
+          else ap += epi.term(v, accP[v / 16][v % 16], invS);
+        }
       }
       if (EPIL && !SMF) {
 #pragma unroll
@@ -1408,7 +1455,46 @@ catalog_score_x3b_kernel(DevParams p, const int64_t* __restrict__ indptr,
     const float Hm = block_max_n<NW>(hmax, red);                        // barrier: chunk published
     const float SA = pow2_scale(Wmax * Hm);
     const float rs = SA / SAcur;                                  // exact power-of-two ratio
-    if (SMF) {
+    if constexpr (ABSE) {
+      // the s tile as below and the L tile beside it: A rows fl(v_k h_jk) scaled by S_l = 2^e with
+      // max|v| Hm S_l in [2^13, 2^14), the same split and products against the same tb. Unscaled
+      // (exact: powers of two), L halved and c0 / 2 added, into the wave's LDS slot; accumulator
+      // register r of lane half hh is tile row 8 (r / 4) + 4 hh + r % 4.
+      const float Sh = pow2_scale(Hm), Sl = pow2_scale(Vmax * Hm);
+      const float is = 1.f / (Sh * St), il = 0.5f / (Sl * St), c0h = 0.5f * vimg[D];
+      const int m = lane & 31;
+      const bool ok = m < jn;
+      floatx16 st, lt;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[r] = lt[r] = 0.f;
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const float* hp = hrows + m * D + hh * DH + 8 * s;
+        const float* vp = vimg + hh * DH + 8 * s;
+        float x[8], y[8];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const float4 h4 = *reinterpret_cast<const float4*>(hp + 4 * q);
+          const float4 v4 = *reinterpret_cast<const float4*>(vp + 4 * q);
+          x[4 * q + 0] = ok ? h4.x * Sh : 0.f; y[4 * q + 0] = ok ? mul_rn(h4.x, v4.x) * Sl : 0.f;
+          x[4 * q + 1] = ok ? h4.y * Sh : 0.f; y[4 * q + 1] = ok ? mul_rn(h4.y, v4.y) * Sl : 0.f;
+          x[4 * q + 2] = ok ? h4.z * Sh : 0.f; y[4 * q + 2] = ok ? mul_rn(h4.z, v4.z) * Sl : 0.f;
+          x[4 * q + 3] = ok ? h4.w * Sh : 0.f; y[4 * q + 3] = ok ? mul_rn(h4.w, v4.w) * Sl : 0.f;
+        }
+        half8 hpc[NPC], lpc[NPC];
+        split_pieces<NPC>(x, hpc);
+        split_pieces<NPC>(y, lpc);
+        st = mfma_pieces<NPC>(hpc, tb[s], st);
+        lt = mfma_pieces<NPC>(lpc, tb[s], lt);
+      }
+      float* ts = tiles + wave * 2048 + (4 * hh) * 32 + m;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = 8 * (r >> 2) + (r & 3);
+        ts[row * 32] = st[r] * is;
+        ts[1024 + row * 32] = __builtin_fmaf(lt[r], il, c0h);
+      }
+    } else if (SMF) {
       const float Sh = pow2_scale(Hm);
       invShSt = 1.f / (Sh * St);
       const int m = lane & 31;
