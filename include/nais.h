@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 21   /* 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 22   /* 22: the New1 model (nais_new1_forward, nais_new1_catalog_tables, nais_new1_score_topk, nais_new1_score_topk_workspace_size; additive); 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -841,6 +841,69 @@ int32_t nais_bpr_train_step(const nais_bpr_params_t* params, const int64_t* user
                             int32_t tag, float* loss_sum, int32_t* err, float* pred_i,
                             float* pred_j, float* g, const nais_bpr_train_grads_t* grads,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * New1 (model.py:830-925; DESIGN.md "New1"): Q / K / V attention over the user's history. With
+ * t = [embed_target[c] | embed_region[treg]] (d floats), h_j the same for history item j,
+ * q = attn_Q t, K_j = attn_K h_j, V_j = attn_V h_j and Kflat the row's contiguous [n, d] key buffer,
+ *   a_j' = sum_e q[e] * Kflat[e * n + j'] / sqrtf(d)   (model.py:896-897: key_emb is RESHAPED to
+ *          [d, n], not transposed; this needs hidden == embed_dim)
+ *   e_j  = expf(a_j) * [hist_j != c]                   (model.py:899-901; no max-subtraction)
+ *   pred = sum_j sum_k (e_j / powf(sum_j e_j, beta) * V_j[k] + r_j * h_j[k]) * t[k];  out = sigmoid(pred)
+ * e_j = inf, all e_j = 0 and a row whose only history item is its target give NaN, as the
+ * reference's. An empty history gives 0.5. At n == 1 the reference's squeeze() calls mix the rows
+ * of the batch (model.py:898-901); here n == 1 is the per-row formula above.
+ *
+ *   nais_new1_forward    out[b] for rows (hist[row * hist_row_stride + j], hist_region likewise,
+ *                        target[row], target_region[row]; int64 ids) and visit_rate[n] shared by
+ *                        the rows: model.py:861-918. hist_row_stride 0 shares one history between
+ *                        the rows (batches.py:355 repeats it). One wave per row: the general path.
+ *                        Ids are device data: a row with an id outside its table is NaN.
+ *   nais_new1_catalog_tables  T[p] = [embed_target[p] | embed_region[region_of[p]]], Q = T attn_Q^T,
+ *                        K = T attn_K^T, V = T attn_V^T, each [P, d] and caller-owned: what
+ *                        model.py:879-893 recompute for every row, once per POI
+ *                        (v_mfma_f32_32x32x2_f32: the fmaf chain over k ascending). A region
+ *                        outside the table makes that POI's rows NaN.
+ *   nais_new1_score_topk replaces the user loop of validation.py:212-230 (batches.py:348-383):
+ *                        for users[num_users] (int32 ids) and the CSR (indptr, indices; rows
+ *                        ascending) with visit_rate[nnz] (r_j per CSR entry, batches.py:358-359 cast
+ *                        to float) the k <= 256 best candidates of [0, P) \ history(u) by
+ *                        sigmoid(pred), as keys for nais_topk_keys_finish (see nais_bpr_score_topk:
+ *                        NaN first, ties by ascending POI id, -0 folded into +0). No score row is
+ *                        written. Its sums over j run in another order than nais_new1_forward's
+ *                        (and it forms sum_j e_j V_j.t before dividing by the power), so the two
+ *                        agree to rounding, not bit for bit; where sum_j e_j overflows with every
+ *                        e_j finite the scorer gives NaN if sum_j e_j V_j.t overflowed too.
+ *                        num_chunks / workspace: as nais_bpr_score_topk.
+ * embed_dim even, 2..256; hidden == embed_dim; num_pois < 2^24 (NAIS_E_UNSUPPORTED otherwise).
+ */
+typedef struct nais_new1_params {
+  int32_t embed_dim;            /* d = embed_size (both halves concatenated)                   */
+  int32_t hidden;               /* attn_Q / attn_K out_features; must equal embed_dim          */
+  int64_t num_pois;             /* P = rows of embed_target                                    */
+  int64_t num_regions;          /* R = rows of embed_region                                    */
+  float beta;                   /* exponent of the softmax denominator (model.py:903)          */
+  const float* embed_target;    /* embed_target.weight [P, d/2]       model.py:837             */
+  const float* embed_region;    /* embed_region.weight [R, d/2]       model.py:839             */
+  const float* attn_q;          /* attn_Q.weight [hidden, d]          model.py:846             */
+  const float* attn_k;          /* attn_K.weight [hidden, d]          model.py:847             */
+  const float* attn_v;          /* attn_V.weight [d, d]               model.py:848             */
+} nais_new1_params_t;
+
+int32_t nais_new1_forward(const nais_new1_params_t* params, const int64_t* hist,
+                          int64_t hist_row_stride, const int64_t* target,
+                          const int64_t* hist_region, const int64_t* target_region,
+                          const float* visit_rate, int64_t b, int64_t n, float* out, void* stream);
+int32_t nais_new1_catalog_tables(const nais_new1_params_t* params, const int64_t* region_of,
+                                 float* T, float* Q, float* K, float* V, void* stream);
+size_t nais_new1_score_topk_workspace_size(const nais_new1_params_t* params, int32_t num_users,
+                                           int32_t k, int32_t num_chunks);
+int32_t nais_new1_score_topk(const nais_new1_params_t* params, const float* T, const float* Q,
+                             const float* K, const float* V, const int64_t* indptr,
+                             const int64_t* indices, const float* visit_rate, const int32_t* users,
+                             int32_t num_users, int32_t k, int32_t num_chunks, uint64_t* keys,
+                             int32_t* kcount, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step of NAIS_basic on one get_NAIS_batch batch (batches.py:24-50):

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -41,7 +41,9 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_geoie_make_train_batch", "nais_geoie_train_step_workspace_size",
            "nais_geoie_train_step", "nais_sgd", "nais_bpr_forward",
            "nais_bpr_score_topk_workspace_size", "nais_bpr_score_topk", "nais_bpr_make_train_batch",
-           "nais_bpr_train_step_workspace_size", "nais_bpr_train_step")
+           "nais_bpr_train_step_workspace_size", "nais_bpr_train_step", "nais_new1_forward",
+           "nais_new1_catalog_tables", "nais_new1_score_topk_workspace_size",
+           "nais_new1_score_topk")
 
 
 class NaisBPRParams(ctypes.Structure):
@@ -49,6 +51,15 @@ class NaisBPRParams(ctypes.Structure):
     _fields_ = [("embed_dim", ctypes.c_int32), ("num_users", ctypes.c_int64),
                 ("num_pois", ctypes.c_int64), ("embed_user", ctypes.c_void_p),
                 ("embed_item", ctypes.c_void_p)]
+
+
+class NaisNew1Params(ctypes.Structure):
+    """Mirror of `nais_new1_params_t` (include/nais.h)."""
+    _fields_ = [("embed_dim", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("num_pois", ctypes.c_int64), ("num_regions", ctypes.c_int64),
+                ("beta", ctypes.c_float), ("embed_target", ctypes.c_void_p),
+                ("embed_region", ctypes.c_void_p), ("attn_q", ctypes.c_void_p),
+                ("attn_k", ctypes.c_void_p), ("attn_v", ctypes.c_void_p)]
 
 
 class NaisBPRTrainGrads(ctypes.Structure):
@@ -327,6 +338,16 @@ def load(path: str | None = None):
     lib.nais_bpr_train_step.argtypes = [ctypes.POINTER(NaisBPRParams), vp, vp, vp, i64, vp, vp, f32,
                                         f32, vp, vp, i32, vp, vp, vp, vp, vp,
                                         ctypes.POINTER(NaisBPRTrainGrads), vp, sz, vp]
+    n1 = ctypes.POINTER(NaisNew1Params)
+    lib.nais_new1_forward.restype = i32
+    lib.nais_new1_forward.argtypes = [n1, vp, i64, vp, vp, vp, vp, i64, i64, vp, vp]
+    lib.nais_new1_catalog_tables.restype = i32
+    lib.nais_new1_catalog_tables.argtypes = [n1, vp, vp, vp, vp, vp, vp]
+    lib.nais_new1_score_topk_workspace_size.restype = sz
+    lib.nais_new1_score_topk_workspace_size.argtypes = [n1, i32, i32, i32]
+    lib.nais_new1_score_topk.restype = i32
+    lib.nais_new1_score_topk.argtypes = [n1, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
+                                         vp, sz, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

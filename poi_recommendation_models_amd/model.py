@@ -1202,3 +1202,154 @@ class BPR(nn.Module):
             return _BPRForward.apply(self, user, item_i, item_j, self.embed_user.weight,
                                      self.embed_item.weight)
         return self._run_forward(user, item_i, item_j)
+
+
+class New1(nn.Module):
+    """New1 (model.py:830-925): `New1(item_num, embed_size, hidden_size, beta, region_embed_size)`
+    with the reference's parameter and state_dict names (`embed_target.weight [P, d/2]`,
+    `embed_region.weight [R, d/2]`, `attn_Q.weight`, `attn_K.weight [H, d]`, `attn_V.weight [d, d]`;
+    no biases), embeddings N(0, 0.01), the Linears torch's default initialisation.
+
+    `forward(history[b, n], target[b], history_region[b, n], target_region[b],
+    history_visit_rate[n])` (each may carry a leading 1; the visit rate arrives as float64 and is
+    cast to float32) returns sigmoid(pred) [b]. On a ROCm device with grad mode off it is the HIP
+    kernel `nais_new1_forward`; under grad mode, or off the device, `restatement` runs: the same
+    formula in torch ops with explicit shapes, so the loop of run_new.py:354-470 trains unchanged.
+    The reference reshapes the key buffer [b, n, H] to [b, d, n] instead of transposing it
+    (model.py:896); both paths reproduce that, and it needs hidden_size == embed_size.
+
+    One deliberate difference: at n == 1 the reference's squeeze() calls drop the history axis and
+    `exp_A * mask` broadcasts to [b, b], mixing the rows of the batch; here n == 1 is the per-row
+    formula. An empty history gives 0.5 (the reference raises).
+
+    The full-catalog evaluation is `new1.score_topk` / `validation.New1_validation`. The device
+    forward checks its ids and raises IndexError, as nn.Embedding would (one flag read back)."""
+
+    def __init__(self, item_num, embed_size, hidden_size, beta, region_embed_size):
+        super().__init__()
+        self.embed_size, self.item_num, self.beta, self.hidden_size = embed_size, item_num, beta, hidden_size
+        self.POI_count = item_num
+        self.embed_target = nn.Embedding(item_num, int(embed_size / 2))
+        self.embed_region = nn.Embedding(region_embed_size, int(embed_size / 2))
+        self.relu = nn.ReLU()
+        self.sigmoid = nn.Sigmoid()
+        self.loss_func = nn.BCELoss()
+        self.attn_Q = nn.Linear(embed_size, hidden_size, bias=False)
+        self.attn_K = nn.Linear(embed_size, hidden_size, bias=False)
+        self.attn_V = nn.Linear(embed_size, embed_size, bias=False)
+        nn.init.normal_(self.embed_target.weight, std=0.01)    # model.py:853-854
+        nn.init.normal_(self.embed_region.weight, std=0.01)
+        self._last_short = None
+
+    def loss_function(self, prediction, label):                # model.py:924-925
+        return self.loss_func(prediction, label)
+
+    def _width(self):
+        d = 2 * int(self.embed_target.weight.shape[1])
+        if (tuple(self.attn_Q.weight.shape) != (d, d) or tuple(self.attn_K.weight.shape) != (d, d)
+                or tuple(self.attn_V.weight.shape) != (d, d)
+                or self.embed_region.weight.shape[1] * 2 != d):
+            raise ValueError("New1: hidden_size must equal embed_size (an even number): the "
+                             "reference reshapes the keys [n, hidden] to [embed, n] (model.py:896)")
+        return d
+
+    @staticmethod
+    def _inputs(history, target, history_region, target_region, history_visit_rate):
+        """The leading 1 of each input dropped (model.py:862-868), by rank rather than squeeze()."""
+        if history.dim() == 3:
+            history = history.reshape(history.shape[1:])
+        if history_region.dim() == 3:
+            history_region = history_region.reshape(history_region.shape[1:])
+        if target.dim() == 2:
+            target = target.reshape(-1)
+        if target_region.dim() == 2:
+            target_region = target_region.reshape(-1)
+        r = history_visit_rate.reshape(-1).to(torch.float32)
+        b, n = history.shape
+        if (target.shape != (b,) or target_region.shape != (b,) or history_region.shape != (b, n)
+                or r.shape != (n,)):
+            raise ValueError(f"New1: history {tuple(history.shape)}, target {tuple(target.shape)}, "
+                             f"history_region {tuple(history_region.shape)}, target_region "
+                             f"{tuple(target_region.shape)}, visit rate {tuple(r.shape)} do not fit")
+        return history, target, history_region, target_region, r
+
+    def restatement(self, history, target, history_region, target_region, history_visit_rate):
+        """model.py:872-918 in torch ops with explicit shapes (differentiable; any device)."""
+        hist, tgt, hreg, treg, r = self._inputs(history, target, history_region, target_region,
+                                                history_visit_rate)
+        d = self._width()
+        b, n = hist.shape
+        h = torch.cat((self.embed_target(hist), self.embed_region(hreg)), -1)      # [b, n, d]
+        t = torch.cat((self.embed_target(tgt), self.embed_region(treg)), -1)       # [b, d]
+        q = self.attn_Q(t)
+        key, val = self.attn_K(h), self.attn_V(h)
+        a = torch.bmm(q.reshape(b, 1, d), key.reshape(b, d, n)).reshape(b, n)      # model.py:896
+        a = a / torch.sqrt(torch.tensor(float(d), device=a.device))
+        e = torch.exp(a) * (hist != tgt.reshape(b, 1))
+        w = e / torch.pow(e.sum(-1), self.beta).reshape(b, 1)
+        res = val * w.reshape(b, n, 1) + h * r.reshape(1, n, 1)
+        pred = torch.bmm(res, t.reshape(b, d, 1)).reshape(b, n).sum(-1)
+        return self.sigmoid(pred)
+
+    def _check_device(self, *tensors):
+        dev = self.embed_target.weight.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"New1: the kernels run only on a ROCm device (parameters are on {dev})")
+        for t in tensors:
+            if t is not None and t.device != dev:
+                raise RuntimeError(f"New1: input on {t.device}, parameters on {dev}")
+        for n, p in self.named_parameters():
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"New1: parameter {n} must be contiguous float32")
+        return dev
+
+    def new1_params(self) -> _capi.NaisNew1Params:
+        """`nais_new1_params_t` view of this module's parameters (device pointers, no copies)."""
+        q = _capi.NaisNew1Params()
+        q.embed_dim = self._width()
+        q.hidden = int(self.attn_Q.weight.shape[0])
+        q.num_pois = int(self.embed_target.weight.shape[0])
+        q.num_regions = int(self.embed_region.weight.shape[0])
+        q.beta = float(self.beta)
+        q.embed_target = self.embed_target.weight.data_ptr()
+        q.embed_region = self.embed_region.weight.data_ptr()
+        q.attn_q = self.attn_Q.weight.data_ptr()
+        q.attn_k = self.attn_K.weight.data_ptr()
+        q.attn_v = self.attn_V.weight.data_ptr()
+        return q
+
+    def _run_forward(self, history, target, history_region, target_region, history_visit_rate):
+        hist, tgt, hreg, treg, r = self._inputs(history, target, history_region, target_region,
+                                                history_visit_rate)
+        dev = self._check_device(hist, tgt, hreg, treg, r)
+        b, n = hist.shape
+        P, R = self.embed_target.weight.shape[0], self.embed_region.weight.shape[0]
+        hist, hreg = hist.to(torch.int64), hreg.to(torch.int64)
+        tgt, treg = tgt.to(torch.int64).contiguous(), treg.to(torch.int64).contiguous()
+        # one history shared by the rows (an expanded view) is read in place, stride 0
+        shared = (b > 0 and n > 0 and hist.stride(0) == 0 and hreg.stride(0) == 0
+                  and hist.stride(1) == 1 and hreg.stride(1) == 1)
+        if not shared:
+            hist, hreg = hist.contiguous(), hreg.contiguous()
+        if b:   # nn.Embedding raises on an id outside its table; the kernel would return NaN
+            hv, rv = (hist[0], hreg[0]) if shared else (hist, hreg)
+            bad = ((tgt < 0) | (tgt >= P)).any() | ((treg < 0) | (treg >= R)).any()
+            if n:
+                bad = bad | ((hv < 0) | (hv >= P)).any() | ((rv < 0) | (rv >= R)).any()
+            if bool(bad):
+                raise IndexError("New1: POI or region id out of range")
+        out = torch.empty(b, dtype=torch.float32, device=dev)
+        r = r.contiguous()
+        _capi.check(_capi.load().nais_new1_forward(
+            self.new1_params(), hist.data_ptr() if n else None, 0 if shared else n, tgt.data_ptr(),
+            hreg.data_ptr() if n else None, treg.data_ptr(), r.data_ptr() if n else None, b, n,
+            out.data_ptr(), _capi.stream_handle(dev)), "nais_new1_forward")
+        return out
+
+    def forward(self, history, target, history_region, target_region, history_visit_rate):
+        on_device = self.embed_target.weight.device.type == "cuda"
+        if on_device and not torch.is_grad_enabled():
+            return self._run_forward(history, target, history_region, target_region,
+                                     history_visit_rate)
+        return self.restatement(history, target, history_region, target_region,
+                                history_visit_rate)

@@ -153,6 +153,25 @@ def BPR_validation(model, args, num_users, test_positive, val_positive, train_ma
     return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
 
 
+def New1_validation(model, args, num_users, test_positive, val_positive, train_matrix,
+                    businessRegionEmbedList, k_list):
+    """validation.py:212-230 (New1): per user the args.topk best POIs outside its training
+    history by the sigmoid score, from the catalog's Q / K / V tables built once per call and one
+    fused scorer + top-k kernel (`new1.score_topk`; no score row is written; the visit rates of
+    batches.py:350-359 are formed on the host in float64). A user with fewer than args.topk
+    candidates raises RuntimeError, as the reference's torch.topk does. Single-process only: there
+    is no distributed New1 evaluation."""
+    import numpy as np
+    from .new1 import score_topk as new1_topk
+    model.eval()                                               # validation.py:214
+    shape = train_matrix.shape
+    hist_len = np.diff(train_matrix.tocsr().indptr)[:num_users]
+    if np.any(shape[1] - hist_len < args.topk):
+        raise RuntimeError("selected index k out of range")   # torch.topk's error
+    ids, _ = new1_topk(model, train_matrix, businessRegionEmbedList, range(num_users), args.topk)
+    return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
+
+
 def new4_validation(model, args, num_users, test_positive, val_positive, train_matrix,
                     businessRegionEmbedList, k_list, nearPOI, distributed=None):
     """validation.py:254-280 (New4): the context tables are built once (the reference rebuilds
