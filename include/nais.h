@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 22   /* 22: the New1 model (nais_new1_forward, nais_new1_catalog_tables, nais_new1_score_topk, nais_new1_score_topk_workspace_size; additive); 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 23   /* 23: New1 training (nais_new1_make_train_batch, nais_new1_train_step, nais_new1_train_step_workspace_size; additive); 22: the New1 model (nais_new1_forward, nais_new1_catalog_tables, nais_new1_score_topk, nais_new1_score_topk_workspace_size; additive); 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -904,6 +904,97 @@ int32_t nais_new1_score_topk(const nais_new1_params_t* params, const float* T, c
                              int32_t num_users, int32_t k, int32_t num_chunks, uint64_t* keys,
                              int32_t* kcount, void* workspace, size_t workspace_bytes,
                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * New1 training (run_new.py:107-137, 389-410, model.py:861-918; DESIGN.md "New1 training"). One
+ * batch is one user (trainDataset.__getitem__, run_new.py:107-137; NOT batches.get_New1_batch,
+ * which shuffles the history after the visit rates are formed): hist[n] = the user's CSR row in
+ * ascending order, visit_rate[n] = data / colsum[hist] (a float64 quotient cast to float32),
+ * b = n * (1 + num_ng) rows target[b] = [pos_i, neg_i1 .. neg_i,num_ng], labels 1 / 0, regions
+ * region_of[.]. With the symbols of the New1 block above, T / Q the b target rows' concatenated
+ * embeddings and attn_Q projections, H / K / V the same for the history and Ks[e][j] =
+ * Kflat[e * n + j] (the [n, d] key buffer read as [d, n], model.py:896):
+ *   A = Q Ks / sqrtf(d)            E[c][j] = expf(A[c][j]) * [hist_j != target_c]
+ *   S_c = sum_j E[c][j]            M = T V^T          g = sum_j r_j h_j
+ *   N_c = sum_j E[c][j] M[c][j]    pred_c = N_c / powf(S_c, beta) + t_c . g
+ *   x_c = sigmoid(pred_c)
+ *   loss = mean_c -(y_c max(log x_c, -100) + (1 - y_c) max(log(1 - x_c), -100))   (nn.BCELoss)
+ *   d_c = (x_c - y_c) / max((1 - x_c) x_c, 1e-12) / b * (1 - x_c) x_c
+ *         -- the composed form autograd produces (BCELoss's backward, then the sigmoid's), NOT
+ *         (x - y) / b: a label-0 row with x == 1.0f has d = 0, and a label-1 row whose
+ *         x (1 - x) is below 1e-12 has |d| < 1 / b
+ *   dM[c][j] = d_c E[c][j] S_c^-beta      dA[c][j] = dM[c][j] (M[c][j] - beta N_c / S_c)
+ *   dQ = dA Ks^T / sqrtf(d)   dKs = Q^T dA / sqrtf(d) -> dKflat[e * n + j] = dKs[e][j]
+ *   dV = dM^T T               dg = sum_c d_c t_c
+ *   dT = dM V + d g^T + dQ Wq             dH = dK Wk + dV Wv + r dg^T
+ *   dWq = dQ^T T    dWk = dK^T H    dWv = dV^T H
+ *   dT / dH scatter into embed_target (the left halves; a positive's row receives its dT and its
+ *   dH share) and embed_region (the right halves; up to b + n shares per row, summed with the
+ *   targets in batch order first, then the history).
+ *   torch.optim.Adam(lr, betas, eps, weight_decay) (run_new.py:389) over EVERY element of the five
+ *   tensors -- dense: a row touched once keeps moving through exp_avg on later steps --
+ *     g' = g + wd p;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2
+ *     p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   the scalars formed in double as Python forms them, then cast to float.
+ *
+ *   nais_new1_make_train_batch  trainDataset.__getitem__ on the device for one user. rate[nnz] =
+ *       the per-entry float64 visit rates (data / colsum), region_of[P] the POI -> region map. The
+ *       negatives are nais_make_train_batch's: the first n * num_ng members of the seeded order
+ *       of [0, P) that are outside the history (the distinct-subset sampler of nais_sampler.h, the
+ *       same seed derivation). *err |= 1, and nothing is written, if n disagrees with indptr or
+ *       n * num_ng > P - n.
+ *   nais_new1_train_step  replaces run_new.py:403-410 for one batch: forward, loss_func, backward
+ *       and optimizer.step(), in place on the five tensors of `params` (written through for this
+ *       call) and on `state`. t = the step number, 1 for the first. *loss_sum (a double: an epoch's
+ *       sum is not rounded to float at every user) += loss; pred[b]
+ *       (optional) = x. grads (optional, any member NULL) receives the five DENSE gradients before
+ *       weight decay, zero outside the touched rows (every element is written). stamp_target /
+ *       stamp_hist: [P] int32 each, zero-initialised once, `tag` a value no earlier step used;
+ *       they mark the touched rows (the rows' slots live in the workspace). *err |= 2 for an id
+ *       outside its table, 1 for a repeated target or history entry, 4 for a NaN prediction (the
+ *       reference raises inside BCELoss there). While *err is non-zero NEITHER parameters NOR
+ *       state are written, so the caller checks and clears it. n >= 2 (at n = 1 the reference's
+ *       positive row has no unmasked item and its step raises), b >= 1. No host sync; no float
+ *       atomics: the same batch from the same state gives the same bits. Exact-fp32 MFMA
+ *       products; the summation order differs from nais_new1_forward's.
+ */
+typedef struct nais_new1_adam_state {
+  float* m_embed_target;        /* exp_avg / exp_avg_sq of embed_target.weight [P, d/2]        */
+  float* v_embed_target;
+  float* m_embed_region;        /* ... of embed_region.weight [R, d/2]                         */
+  float* v_embed_region;
+  float* m_attn_q;              /* ... of attn_Q.weight [d, d]                                 */
+  float* v_attn_q;
+  float* m_attn_k;              /* ... of attn_K.weight [d, d]                                 */
+  float* v_attn_k;
+  float* m_attn_v;              /* ... of attn_V.weight [d, d]                                 */
+  float* v_attn_v;
+} nais_new1_adam_state_t;
+
+typedef struct nais_new1_train_grads {
+  float* embed_target;          /* [P, d/2] dense                                              */
+  float* embed_region;          /* [R, d/2] dense                                              */
+  float* attn_q;                /* [d, d]                                                      */
+  float* attn_k;                /* [d, d]                                                      */
+  float* attn_v;                /* [d, d]                                                      */
+} nais_new1_train_grads_t;
+
+int32_t nais_new1_make_train_batch(const int64_t* indptr, const int64_t* indices,
+                                   const double* rate, const int64_t* region_of, int64_t user,
+                                   int64_t n, int64_t num_pois, int32_t num_ng, uint64_t seed,
+                                   int64_t* hist, int64_t* hist_region, float* visit_rate,
+                                   int64_t* target, int64_t* target_region, float* labels,
+                                   int32_t* err, void* stream);
+size_t nais_new1_train_step_workspace_size(const nais_new1_params_t* params, int64_t b, int64_t n);
+int32_t nais_new1_train_step(const nais_new1_params_t* params, const int64_t* hist,
+                             const int64_t* hist_region, const float* visit_rate,
+                             const int64_t* target, const int64_t* target_region,
+                             const float* labels, int64_t b, int64_t n, double lr,
+                             double weight_decay, double beta1, double beta2, double eps,
+                             int64_t t, const nais_new1_adam_state_t* state, int32_t* stamp_target,
+                             int32_t* stamp_hist, int32_t tag, double* loss_sum, int32_t* err,
+                             float* pred, const nais_new1_train_grads_t* grads, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training step of NAIS_basic on one get_NAIS_batch batch (batches.py:24-50):

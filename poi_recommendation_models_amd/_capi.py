@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libnais_hip.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 PRECISION_FP32, PRECISION_FP16X3, PRECISION_FP16X3_PAIRSPLIT = 0, 1, 2
 PRIOR_FINITE = 1   # nais_pair_prior_gather flags (include/nais.h NAIS_PRIOR_FINITE)
 PRECISION_FP16X6, PRECISION_FP16X6_PAIRSPLIT = 3, 4
@@ -43,7 +43,8 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_bpr_score_topk_workspace_size", "nais_bpr_score_topk", "nais_bpr_make_train_batch",
            "nais_bpr_train_step_workspace_size", "nais_bpr_train_step", "nais_new1_forward",
            "nais_new1_catalog_tables", "nais_new1_score_topk_workspace_size",
-           "nais_new1_score_topk")
+           "nais_new1_score_topk", "nais_new1_make_train_batch",
+           "nais_new1_train_step_workspace_size", "nais_new1_train_step")
 
 
 class NaisBPRParams(ctypes.Structure):
@@ -60,6 +61,18 @@ class NaisNew1Params(ctypes.Structure):
                 ("beta", ctypes.c_float), ("embed_target", ctypes.c_void_p),
                 ("embed_region", ctypes.c_void_p), ("attn_q", ctypes.c_void_p),
                 ("attn_k", ctypes.c_void_p), ("attn_v", ctypes.c_void_p)]
+
+
+class NaisNew1AdamState(ctypes.Structure):
+    """Mirror of `nais_new1_adam_state_t` (include/nais.h): exp_avg / exp_avg_sq per parameter."""
+    _fields_ = [(f"{k}_{n}", ctypes.c_void_p) for n in ("embed_target", "embed_region", "attn_q",
+                                                        "attn_k", "attn_v") for k in ("m", "v")]
+
+
+class NaisNew1TrainGrads(ctypes.Structure):
+    """Mirror of `nais_new1_train_grads_t` (include/nais.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("embed_target", "embed_region", "attn_q", "attn_k",
+                                               "attn_v")]
 
 
 class NaisBPRTrainGrads(ctypes.Structure):
@@ -348,6 +361,15 @@ def load(path: str | None = None):
     lib.nais_new1_score_topk.restype = i32
     lib.nais_new1_score_topk.argtypes = [n1, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp,
                                          vp, sz, vp]
+    lib.nais_new1_make_train_batch.restype = i32
+    lib.nais_new1_make_train_batch.argtypes = [vp, vp, vp, vp, i64, i64, i64, i32, u64, vp, vp, vp,
+                                               vp, vp, vp, vp, vp]
+    lib.nais_new1_train_step_workspace_size.restype = sz
+    lib.nais_new1_train_step_workspace_size.argtypes = [n1, i64, i64]
+    lib.nais_new1_train_step.restype = i32
+    lib.nais_new1_train_step.argtypes = [n1, vp, vp, vp, vp, vp, vp, i64, i64, f64, f64, f64, f64,
+                                         f64, i64, ctypes.POINTER(NaisNew1AdamState), vp, vp, i32,
+                                         vp, vp, vp, ctypes.POINTER(NaisNew1TrainGrads), vp, sz, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

@@ -31,6 +31,11 @@ loss_function, backward and torch.optim.SGD in place on the four embedding table
 `BPRTrainer` is train_BPR's loop (run.py:490-509): `nais_bpr_make_train_batch` is get_BPR_batch
 (batches.py:6-22) for a whole list of users and `nais_bpr_train_step` is forward, the BPR loss,
 backward and torch.optim.SGD in place on both tables, deterministic (no float atomics).
+
+`New1Trainer` is train_NAIS_new's loop (run_new.py:391-410): `nais_new1_make_train_batch` is
+trainDataset.__getitem__ (run_new.py:107-137) on the device and `nais_new1_train_step` is forward,
+nn.BCELoss, backward and torch.optim.Adam (dense, with weight decay) in place on the five
+parameter tensors, deterministic.
 """
 from __future__ import annotations
 
@@ -557,3 +562,217 @@ class BPRTrainer:
             raise RuntimeError(f"BPRTrainer: an id outside its table or an undrawable batch (code {err}); "
                                "that step and the later ones were not applied")
         return float(self.loss_sum.item())
+
+
+class New1Trainer:
+    """train_NAIS_new's loop (run_new.py:391-410) on the device: `batch()` is
+    trainDataset.__getitem__ (run_new.py:107-137), `step()` is run_new.py:403-410 (forward,
+    loss_func = nn.BCELoss, backward, torch.optim.Adam(lr, betas, eps, weight_decay), which is
+    dense: every element of the five tensors moves on every step) updating the model in place,
+    `epoch()` the loop with one host sync at its end. Adam's exp_avg / exp_avg_sq live in the
+    trainer (`optimizer_state()` / `load_optimizer_state()` exchange them with torch.optim.Adam).
+    A step is deterministic: the same batch from the same state gives the same bits.
+
+    The reference cannot train on a user with fewer than 2 history items (its positive row has no
+    unmasked item, 0 / 0 is NaN and BCELoss raises): `step()` raises ValueError there and
+    `epoch()` skips such users, counting them in `skipped_users`."""
+
+    NAMES = ("embed_target.weight", "embed_region.weight", "attn_Q.weight", "attn_K.weight",
+             "attn_V.weight")
+    _FIELDS = ("embed_target", "embed_region", "attn_q", "attn_k", "attn_v")
+
+    def __init__(self, model, train_matrix, region_of, lr=0.01, weight_decay=1e-7, num_ng=4,
+                 betas=(0.9, 0.999), eps=1e-8):
+        from .model import New1
+        from .new1 import _region_tensor, visit_rates
+        if not isinstance(model, New1):
+            raise NotImplementedError(f"New1Trainer: {type(model).__name__} is not New1")
+        dev = model._check_device()
+        if int(num_ng) < 1:
+            raise ValueError(f"New1Trainer: num_ng must be at least 1, got {num_ng}")
+        self.model, self.dev = model, dev
+        X, r64 = visit_rates(train_matrix)
+        self.csr = device_csr(X, dev)
+        P = model.embed_target.weight.shape[0]
+        if self.csr.shape[1] != P:
+            raise ValueError(f"train_matrix has {self.csr.shape[1]} POIs, model has {P}")
+        self.region_of = _region_tensor(model, region_of, dev)
+        self.rate = torch.from_numpy(np.ascontiguousarray(r64, dtype=np.float64)).to(dev)
+        self.num_ng, self.lr, self.weight_decay = int(num_ng), float(lr), float(weight_decay)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.step_count = 0        # Adam's step number t
+        self._tag = 0              # one stamp value per call, also for a step that set err
+        self.skipped_users = 0
+        ps = dict(model.named_parameters())
+        self.exp_avg = {k: torch.zeros_like(ps[k]) for k in self.NAMES}
+        self.exp_avg_sq = {k: torch.zeros_like(ps[k]) for k in self.NAMES}
+        self._st_t = torch.zeros(P, dtype=torch.int32, device=dev)
+        self._st_h = torch.zeros(P, dtype=torch.int32, device=dev)
+        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._ws = torch.empty(0, dtype=torch.uint8, device=dev)
+        self._bufs = {}
+
+    def _check_user(self, uid):
+        n = int(self.csr.hist_len[uid])
+        P = self.csr.shape[1]
+        if n < 1:
+            raise ValueError(f"New1: empty history (user {int(uid)})")
+        if n * self.num_ng > P - n:
+            raise ValueError(f"user {int(uid)}: {n} positives x {self.num_ng} negatives exceed the "
+                             f"{P - n} POIs outside the history (trainDataset cannot draw them)")
+        return n
+
+    def batch(self, uid, seed=None):
+        """trainDataset.__getitem__(uid) (run_new.py:107-137) on the device: (hist [n], target [b],
+        labels [b], hist_region [n], target_region [b], visit_rate [n] f32), b = n (1 + num_ng);
+        the reference's user_history is hist repeated b times. The history is the CSR row in
+        ascending order, the negatives are distinct and uniform over the POIs outside it. The
+        buffers are reused by the next call of the same shape."""
+        n = self._check_user(uid)
+        b = n * (1 + self.num_ng)
+        if n not in self._bufs:
+            d = self.dev
+            self._bufs = {n: (torch.empty(n, dtype=torch.int64, device=d),
+                              torch.empty(b, dtype=torch.int64, device=d),
+                              torch.empty(b, dtype=torch.float32, device=d),
+                              torch.empty(n, dtype=torch.int64, device=d),
+                              torch.empty(b, dtype=torch.int64, device=d),
+                              torch.empty(n, dtype=torch.float32, device=d))}
+        hist, tgt, lab, hreg, treg, vr = self._bufs[n]
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        _capi.check(_capi.load().nais_new1_make_train_batch(
+            self.csr.indptr.data_ptr(), self.csr.indices.data_ptr(), self.rate.data_ptr(),
+            self.region_of.data_ptr(), int(uid), n, self.csr.shape[1], self.num_ng, seed,
+            hist.data_ptr(), hreg.data_ptr(), vr.data_ptr(), tgt.data_ptr(), treg.data_ptr(),
+            lab.data_ptr(), self._err.data_ptr(), _capi.stream_handle(self.dev)),
+            "nais_new1_make_train_batch")
+        return hist, tgt, lab, hreg, treg, vr
+
+    def _state_struct(self):
+        s = _capi.NaisNew1AdamState()
+        for name, f in zip(self.NAMES, self._FIELDS):
+            setattr(s, "m_" + f, self.exp_avg[name].data_ptr())
+            setattr(s, "v_" + f, self.exp_avg_sq[name].data_ptr())
+        return s
+
+    def step(self, hist, target, labels, hist_region, target_region, visit_rate, pred=None,
+             grads=None):
+        """One fused step (run_new.py:403-410) on a batch as batch() returns it, or in the
+        reference's own layout: user_history / user_history_region [b, n] with equal rows (row 0
+        is taken; the reference repeats one history, run_new.py:111, 132), any input with a
+        leading 1 (the DataLoader's batch axis), the visit rate as float64. `pred`: optional [b]
+        f32 output (sigmoid(pred)); `grads`: optional dict that receives the five dense gradients
+        (before weight decay) under the parameter names."""
+        m = self.model
+        dev = m._check_device(hist, target, labels, hist_region, target_region, visit_rate)
+        if hist.dim() == 3:
+            hist = hist.reshape(hist.shape[1:])
+        if hist_region.dim() == 3:
+            hist_region = hist_region.reshape(hist_region.shape[1:])
+        if hist.dim() == 2:
+            hist = hist[0] if hist.shape[0] else hist.new_empty(0)
+        if hist_region.dim() == 2:
+            hist_region = hist_region[0] if hist_region.shape[0] else hist_region.new_empty(0)
+        hist = hist.reshape(-1).to(torch.int64).contiguous()
+        hreg = hist_region.reshape(-1).to(torch.int64).contiguous()
+        target = target.reshape(-1).to(torch.int64).contiguous()
+        treg = target_region.reshape(-1).to(torch.int64).contiguous()
+        labels = labels.reshape(-1).to(torch.float32).contiguous()
+        vr = visit_rate.reshape(-1).to(torch.float32).contiguous()
+        b, n = target.numel(), hist.numel()
+        if n < 2:
+            raise ValueError(f"New1: a history of {n} item(s) cannot be trained on: the reference's "
+                             "positive row has no unmasked history item, its prediction is NaN and "
+                             "BCELoss raises (all elements of input should be between 0 and 1)")
+        if b < 1 or labels.numel() != b or treg.numel() != b or hreg.numel() != n or vr.numel() != n:
+            raise ValueError(f"labels / target_region must hold b = {b} rows (b >= 1), hist_region / "
+                             f"visit_rate n = {n}; got {labels.numel()}, {treg.numel()}, "
+                             f"{hreg.numel()}, {vr.numel()}")
+        if pred is not None and (pred.dtype != torch.float32 or pred.numel() != b
+                                 or not pred.is_contiguous()):
+            raise ValueError("pred must be a contiguous float32 tensor of b elements")
+        gs = _capi.NaisNew1TrainGrads()
+        if grads is not None:
+            ps = dict(m.named_parameters())
+            for name, f in zip(self.NAMES, self._FIELDS):
+                g = torch.empty_like(ps[name])
+                grads[name] = g
+                setattr(gs, f, g.data_ptr())
+        lib = _capi.load()
+        prm = m.new1_params()
+        need = lib.nais_new1_train_step_workspace_size(prm, b, n)
+        if self._ws.numel() < need:
+            self._ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=dev)
+        self.step_count += 1
+        self._tag += 1
+        _capi.check(lib.nais_new1_train_step(
+            prm, hist.data_ptr(), hreg.data_ptr(), vr.data_ptr(), target.data_ptr(), treg.data_ptr(),
+            labels.data_ptr(), b, n, self.lr, self.weight_decay, self.betas[0], self.betas[1],
+            self.eps, self.step_count, self._state_struct(), self._st_t.data_ptr(),
+            self._st_h.data_ptr(), self._tag, self.loss_sum.data_ptr(), self._err.data_ptr(),
+            _capi.ptr(pred), gs if grads is not None else None, self._ws.data_ptr(),
+            self._ws.numel(), _capi.stream_handle(dev)), "nais_new1_train_step")
+        self._bump_versions()
+
+    def _bump_versions(self):
+        """As NAISTrainer._bump_versions: the step writes through raw pointers."""
+        for q in self.model.parameters():
+            increment_version(q)
+
+    def epoch(self, users=None, shuffle=True):
+        """run_new.py:396-410 over `users` (default: every user, shuffled as the DataLoader of
+        run_new.py:383 shuffles them). Users with fewer than 2 history items are skipped and
+        counted in `skipped_users` (the reference cannot train on them either). Returns train_loss
+        (the sum of the per-batch mean losses, run_new.py:408), read with the epoch's one host
+        sync."""
+        if users is None:
+            users = np.arange(self.csr.shape[0])
+        users = np.asarray(users, dtype=np.int64)
+        if shuffle:
+            users = users[torch.randperm(len(users)).numpy()]
+        self.model.train()
+        self.loss_sum.zero_()
+        for u in users.tolist():
+            if int(self.csr.hist_len[u]) < 2:
+                self.skipped_users += 1
+                continue
+            self.step(*self.batch(u))
+        return self.finish()
+
+    def finish(self):
+        """Host sync: the accumulated loss. Raises if a step saw a repeated target or history
+        entry, an id outside its table, a history length that disagrees with the CSR or a NaN
+        prediction (the reference raises inside BCELoss there); that step and every later one
+        left parameters and state untouched."""
+        err = int(self._err.item())
+        if err:
+            self._err.zero_()
+            raise RuntimeError("New1Trainer: a batch had a repeated target or history entry, a "
+                               "history length that disagrees with the CSR (1), an id outside its "
+                               "table (2) or a NaN prediction (4: all elements of input should be "
+                               f"between 0 and 1) (code {err}); that step and the later ones were "
+                               "not applied")
+        return float(self.loss_sum.item())
+
+    def optimizer_state(self):
+        """torch.optim.Adam's per-parameter state {name: {'step', 'exp_avg', 'exp_avg_sq'}} (the
+        tensors are the trainer's own, not copies)."""
+        return {k: {"step": torch.tensor(float(self.step_count)), "exp_avg": self.exp_avg[k],
+                    "exp_avg_sq": self.exp_avg_sq[k]} for k in self.NAMES}
+
+    def load_optimizer_state(self, state):
+        """The inverse of optimizer_state(): {name: {'step', 'exp_avg', 'exp_avg_sq'}}, e.g. built
+        from torch.optim.Adam's state. Every parameter must be present with one common step."""
+        steps = {int(float(state[k]["step"])) for k in self.NAMES}
+        if len(steps) != 1:
+            raise ValueError(f"New1Trainer: the parameters' step counts differ: {sorted(steps)}")
+        for k in self.NAMES:
+            for key, dst in (("exp_avg", self.exp_avg[k]), ("exp_avg_sq", self.exp_avg_sq[k])):
+                src = state[k][key]
+                if tuple(src.shape) != tuple(dst.shape):
+                    raise ValueError(f"New1Trainer: {k} {key} is {tuple(src.shape)}, "
+                                     f"expected {tuple(dst.shape)}")
+                dst.copy_(src.to(device=self.dev, dtype=torch.float32))
+        self.step_count = steps.pop()
