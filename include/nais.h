@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define NAIS_ABI_VERSION 23   /* 23: New1 training (nais_new1_make_train_batch, nais_new1_train_step, nais_new1_train_step_workspace_size; additive); 22: the New1 model (nais_new1_forward, nais_new1_catalog_tables, nais_new1_score_topk, nais_new1_score_topk_workspace_size; additive); 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
+#define NAIS_ABI_VERSION 23   /* still 23 with the New2 model (nais_new2_forward, nais_new2_score_topk, nais_new2_score_topk_workspace_size, nais_new2_params_t): new entry points and one new struct only, no existing layout or behaviour moves, so the number did not change; 23: New1 training (nais_new1_make_train_batch, nais_new1_train_step, nais_new1_train_step_workspace_size; additive); 22: the New1 model (nais_new1_forward, nais_new1_catalog_tables, nais_new1_score_topk, nais_new1_score_topk_workspace_size; additive); 21: the BPR model (nais_bpr_forward, nais_bpr_score_topk, nais_bpr_score_topk_workspace_size, nais_bpr_make_train_batch, nais_bpr_train_step, nais_bpr_train_step_workspace_size; additive); 20: block-scaled 16-bit pair words for the bounded gather ("q16": nais_pair_table_bound1_q16_queued, nais_pair_bound_topk_q16, nais_q16_pitch; additive); 19: GeoIE training (nais_geoie_make_train_batch, nais_geoie_train_step, nais_geoie_train_step_workspace_size, nais_sgd; additive); 18: the GeoIE model (nais_geoie_table, nais_geoie_score, nais_geoie_forward; additive); 17: nais_pair_table_bound1_queued (the bound table with one f16 product per attention-logit term; additive); 16: nais_pair_table_bound_queued (the 3-product bound table as a work queue; additive), and the item-side fp16x3 table kernel takes nais_pair_table's / nais_pair_table_split's work counter too (as does fp16x6 at embed_dim 16, the same kernel); 15: on-demand exact refine of the bounded gather (nais_pair_table_bound, nais_pair_scales, nais_pair_bound_topk_widened, nais_pair_refine_topk_exact, nais_pair_recompute; additive); 14: nais_pair_bound_topk / nais_pair_refine_topk take the optional per-entry table rows and per-slot history spans; 13: split16 pair tables, bounded gather + exact refine (nais_pair_table_split, nais_pair_bound_topk, nais_pair_refine_topk); 12: any embed_dim <= 256 and any hidden (generic-shape kernels); 11: hidden up to 256 (fp16x6 scoring, nais_forward), any variant on the x6n kernel */
 
 /* model variants */
 #define NAIS_VARIANT_BASIC 0           /* NAIS_basic                      model.py:8-97    */
@@ -994,6 +994,66 @@ int32_t nais_new1_train_step(const nais_new1_params_t* params, const int64_t* hi
                              int64_t t, const nais_new1_adam_state_t* state, int32_t* stamp_target,
                              int32_t* stamp_hist, int32_t tag, double* loss_sum, int32_t* err,
                              float* pred, const nais_new1_train_grads_t* grads, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * New2 (model.py:927-1027, run_new.py:173-264, 468-584; DESIGN.md "New2"): New1 plus a geographic
+ * weight per (row, history item). With New1's symbols, w = embed_dist[uid] (R floats), b rows and
+ * n history items:
+ *   G[j]      = sum_c w[target_region[c]] * w[hist_region[c][j]]   (model.py:1008: a [b] @ [b, n]
+ *               product; it sums over THE BATCH and is the same for every row)
+ *   lambda[j] = -1 / (relu(G[j]) + 1)
+ *   D'[c][j]  = dist[c * n + j]     (dist arrives as [n, b] = history rows x target columns and is
+ *               RESHAPED to [b, n], not transposed: flat index f = c n + j holds the distance of
+ *               history item f div b and target f mod b)
+ *   geo[c][j] = expf(lambda[j] * D'[c][j])                         (not masked)
+ *   pred_c    = sum_j (e_cj / powf(S_c, beta) + geo[c][j]) (V_j . t_c)  +  t_c . sum_j r_j h_j
+ * Both oddities are the reference's and are reproduced. NaN rules, n == 0 and n == 1 as New1.
+ *
+ *   nais_new2_forward    out[b] for rows as nais_new1_forward's, dist[n * b] float32 read flat,
+ *                        uid a host value. lambda_work[n] is scratch: lambda[j] is reduced over
+ *                        the batch first, in a fixed order (no float atomics: same input, same
+ *                        bits), then one wave per row. A row with an id outside its table is NaN;
+ *                        a uid or a region id outside embed_dist makes G, so every row, NaN.
+ *   nais_new2_score_topk the evaluation loop of run_new.py:551-570 (testDataset2.__getitem__,
+ *                        run_new.py:242-264): nais_new1_score_topk with the geo term. The batch of
+ *                        user u is its complement [0, P) \ history(u) in ascending POI id, b = P - n
+ *                        rows that share the history, so G[j] = w[region_of[hist_j]] * sigma_u with
+ *                        sigma_u = sum over the candidates of w[region_of[c]] (per-region counts,
+ *                        float64, rounded once), and the row of the c-th candidate BY POSITION
+ *                        pairs history item (c n + j) div b with the candidate at POSITION
+ *                        (c n + j) mod b. T, Q, K, V are nais_new1_catalog_tables' (call it with
+ *                        &params->base). The distances come from exactly one of
+ *                          coords   [P, 2] float64 (lat, lng in degrees): the haversine package's
+ *                                   formula evaluated per pair on the device in float64, in its
+ *                                   operation order, kilometres (mean radius 6371.0088), rounded
+ *                                   to float32; nothing P x P is allocated;
+ *                          dist_mat [P, P] float32, row-major, the caller's.
+ *                        users[.] indexes the CSR rows and embed_dist (a user outside embed_dist
+ *                        scores NaN). Keys, order rules, num_chunks as nais_new1_score_topk; the
+ *                        workspace (always needed) also holds the per-region counts and the
+ *                        per-POI coordinate table.
+ * nais_new2_params_t embeds New1's struct first, so &params->base is a nais_new1_params_t.
+ */
+typedef struct nais_new2_params {
+  nais_new1_params_t base;      /* New1's fields (model.py:935-946)                             */
+  int64_t num_users;            /* U = rows of embed_dist                                       */
+  const float* embed_dist;      /* embed_dist [U, R]                  model.py:938              */
+} nais_new2_params_t;
+
+int32_t nais_new2_forward(const nais_new2_params_t* params, const int64_t* hist,
+                          int64_t hist_row_stride, const int64_t* target,
+                          const int64_t* hist_region, const int64_t* target_region,
+                          const float* visit_rate, const float* dist, int64_t uid, int64_t b,
+                          int64_t n, float* lambda_work, float* out, void* stream);
+size_t nais_new2_score_topk_workspace_size(const nais_new2_params_t* params, int32_t num_users,
+                                           int32_t k, int32_t num_chunks);
+int32_t nais_new2_score_topk(const nais_new2_params_t* params, const float* T, const float* Q,
+                             const float* K, const float* V, const int64_t* region_of,
+                             const int64_t* indptr, const int64_t* indices,
+                             const float* visit_rate, const double* coords, const float* dist_mat,
+                             const int32_t* users, int32_t num_users, int32_t k,
+                             int32_t num_chunks, uint64_t* keys, int32_t* kcount, void* workspace,
                              size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------

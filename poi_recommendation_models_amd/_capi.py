@@ -44,7 +44,8 @@ EXPORTS = ("nais_abi_version", "nais_last_error", "nais_forward", "nais_score_to
            "nais_bpr_train_step_workspace_size", "nais_bpr_train_step", "nais_new1_forward",
            "nais_new1_catalog_tables", "nais_new1_score_topk_workspace_size",
            "nais_new1_score_topk", "nais_new1_make_train_batch",
-           "nais_new1_train_step_workspace_size", "nais_new1_train_step")
+           "nais_new1_train_step_workspace_size", "nais_new1_train_step", "nais_new2_forward",
+           "nais_new2_score_topk_workspace_size", "nais_new2_score_topk")
 
 
 class NaisBPRParams(ctypes.Structure):
@@ -61,6 +62,12 @@ class NaisNew1Params(ctypes.Structure):
                 ("beta", ctypes.c_float), ("embed_target", ctypes.c_void_p),
                 ("embed_region", ctypes.c_void_p), ("attn_q", ctypes.c_void_p),
                 ("attn_k", ctypes.c_void_p), ("attn_v", ctypes.c_void_p)]
+
+
+class NaisNew2Params(ctypes.Structure):
+    """Mirror of `nais_new2_params_t` (include/nais.h): New1's struct first, then embed_dist."""
+    _fields_ = [("base", NaisNew1Params), ("num_users", ctypes.c_int64),
+                ("embed_dist", ctypes.c_void_p)]
 
 
 class NaisNew1AdamState(ctypes.Structure):
@@ -370,6 +377,14 @@ def load(path: str | None = None):
     lib.nais_new1_train_step.argtypes = [n1, vp, vp, vp, vp, vp, vp, i64, i64, f64, f64, f64, f64,
                                          f64, i64, ctypes.POINTER(NaisNew1AdamState), vp, vp, i32,
                                          vp, vp, vp, ctypes.POINTER(NaisNew1TrainGrads), vp, sz, vp]
+    n2 = ctypes.POINTER(NaisNew2Params)
+    lib.nais_new2_forward.restype = i32
+    lib.nais_new2_forward.argtypes = [n2, vp, i64, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp]
+    lib.nais_new2_score_topk_workspace_size.restype = sz
+    lib.nais_new2_score_topk_workspace_size.argtypes = [n2, i32, i32, i32]
+    lib.nais_new2_score_topk.restype = i32
+    lib.nais_new2_score_topk.argtypes = [n2, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                         i32, vp, vp, vp, sz, vp]
     lib.nais_stream_create_cu_mask.restype = i32
     lib.nais_stream_create_cu_mask.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
     lib.nais_stream_destroy.restype = i32

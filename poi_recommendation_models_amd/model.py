@@ -1353,3 +1353,115 @@ class New1(nn.Module):
                                      history_visit_rate)
         return self.restatement(history, target, history_region, target_region,
                                 history_visit_rate)
+
+
+class New2(New1):
+    """New2 (model.py:927-1027): `New2(item_num, embed_size, hidden_size, beta, region_embed_size,
+    user_num)`: New1 plus the bare parameter `embed_dist [user_num, region_embed_size]`, N(0, 0.01)
+    (the reference's names and initialisation), which weights every (row, history item) pair by
+    geography. With w = embed_dist[uid]:
+
+        G[j]      = sum_c w[target_region[c]] * w[history_region[c][j]]   over THE BATCH (model.py:1008)
+        geo[c][j] = exp(-1 / (relu(G[j]) + 1) * dist.reshape(b, n)[c][j])
+        pred_c    = sum_j (attention weight + geo)[c][j] * (V_j . t_c) + t_c . sum_j r_j h_j
+
+    `forward(history, target, history_region, target_region, history_visit_rate, dist_mat, uid)`:
+    the first five as New1's (each may carry a leading 1); `dist_mat` holds n * b distances (the
+    reference passes [n, b] = history rows x target columns and RESHAPES it to [b, n]; it is read
+    flat, whatever its shape, and cast to float32; another element count raises ValueError); `uid`
+    is an int or a 0-dim tensor. Both oddities -- the batch-wide G and the reshape -- are the
+    reference's and are reproduced. On a ROCm device with grad mode off the forward is the HIP
+    kernel `nais_new2_forward`; under grad mode, or off the device, `restatement` runs, so the loop
+    of run_new.py:505-527 trains unchanged. n == 1 and n == 0 as New1.
+
+    The full-catalog evaluation is `new2.score_topk` / `validation.New2_validation`."""
+
+    def __init__(self, item_num, embed_size, hidden_size, beta, region_embed_size, user_num):
+        super().__init__(item_num, embed_size, hidden_size, beta, region_embed_size)
+        self.user_num = user_num
+        self.embed_dist = nn.Parameter(torch.normal(0.0, 0.01, (user_num, region_embed_size)))   # model.py:938
+
+    @staticmethod
+    def _dist(dist_mat, b, n):
+        dist = dist_mat.reshape(-1)
+        if dist.numel() != b * n:
+            raise ValueError(f"New2: dist_mat has {dist.numel()} elements, the batch needs "
+                             f"n * b = {n} * {b}")
+        return dist.to(torch.float32)
+
+    def restatement(self, history, target, history_region, target_region, history_visit_rate,
+                    dist_mat, uid):
+        """model.py:970-1020 in torch ops with explicit shapes (differentiable; any device)."""
+        hist, tgt, hreg, treg, r = self._inputs(history, target, history_region, target_region,
+                                                history_visit_rate)
+        d = self._width()
+        b, n = hist.shape
+        dist = self._dist(dist_mat, b, n).reshape(b, n)
+        w_u = self.embed_dist[int(uid)]                                            # [R]
+        h = torch.cat((self.embed_target(hist), self.embed_region(hreg)), -1)      # [b, n, d]
+        t = torch.cat((self.embed_target(tgt), self.embed_region(treg)), -1)       # [b, d]
+        q = self.attn_Q(t)
+        key, val = self.attn_K(h), self.attn_V(h)
+        a = torch.bmm(q.reshape(b, 1, d), key.reshape(b, d, n)).reshape(b, n)      # model.py:996
+        a = a / torch.sqrt(torch.tensor(float(d), device=a.device))
+        e = torch.exp(a) * (hist != tgt.reshape(b, 1))
+        w = e / torch.pow(e.sum(-1), self.beta).reshape(b, 1)
+        G = (w_u[treg].reshape(b, 1) * w_u[hreg]).sum(0)                           # [n]: over the batch
+        geo = torch.exp(-1 / (self.relu(G) + 1.0) * dist)                          # model.py:1008
+        res = val * (w + geo).reshape(b, n, 1) + h * r.reshape(1, n, 1)
+        pred = torch.bmm(res, t.reshape(b, d, 1)).reshape(b, n).sum(-1)
+        return self.sigmoid(pred)
+
+    def new2_params(self) -> _capi.NaisNew2Params:
+        """`nais_new2_params_t` view of this module's parameters (device pointers, no copies)."""
+        q = _capi.NaisNew2Params()
+        q.base = self.new1_params()
+        q.num_users = int(self.embed_dist.shape[0])
+        q.embed_dist = self.embed_dist.data_ptr()
+        if tuple(self.embed_dist.shape) != (q.num_users, q.base.num_regions):
+            raise ValueError("New2: embed_dist must be [user_num, region_embed_size]")
+        return q
+
+    def _run_forward(self, history, target, history_region, target_region, history_visit_rate,
+                     dist_mat, uid):
+        hist, tgt, hreg, treg, r = self._inputs(history, target, history_region, target_region,
+                                                history_visit_rate)
+        b, n = hist.shape
+        dist = self._dist(dist_mat, b, n)
+        dev = self._check_device(hist, tgt, hreg, treg, r, dist)
+        uid = int(uid)
+        P, R = self.embed_target.weight.shape[0], self.embed_region.weight.shape[0]
+        hist, hreg = hist.to(torch.int64), hreg.to(torch.int64)
+        tgt, treg = tgt.to(torch.int64).contiguous(), treg.to(torch.int64).contiguous()
+        # one history shared by the rows (an expanded view) is read in place, stride 0
+        shared = (b > 0 and n > 0 and hist.stride(0) == 0 and hreg.stride(0) == 0
+                  and hist.stride(1) == 1 and hreg.stride(1) == 1)
+        if not shared:
+            hist, hreg = hist.contiguous(), hreg.contiguous()
+        if not 0 <= uid < self.embed_dist.shape[0]:
+            raise IndexError("New2: uid out of range")
+        if b:   # nn.Embedding raises on an id outside its table; the kernel would return NaN
+            hv, rv = (hist[0], hreg[0]) if shared else (hist, hreg)
+            bad = ((tgt < 0) | (tgt >= P)).any() | ((treg < 0) | (treg >= R)).any()
+            if n:
+                bad = bad | ((hv < 0) | (hv >= P)).any() | ((rv < 0) | (rv >= R)).any()
+            if bool(bad):
+                raise IndexError("New2: POI or region id out of range")
+        out = torch.empty(b, dtype=torch.float32, device=dev)
+        lam = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+        r, dist = r.contiguous(), dist.contiguous()
+        _capi.check(_capi.load().nais_new2_forward(
+            self.new2_params(), hist.data_ptr() if n else None, 0 if shared else n, tgt.data_ptr(),
+            hreg.data_ptr() if n else None, treg.data_ptr(), r.data_ptr() if n else None,
+            dist.data_ptr() if n else None, uid, b, n, lam.data_ptr(), out.data_ptr(),
+            _capi.stream_handle(dev)), "nais_new2_forward")
+        return out
+
+    def forward(self, history, target, history_region, target_region, history_visit_rate,
+                dist_mat, uid):                                   # model.py:959-968
+        on_device = self.embed_target.weight.device.type == "cuda"
+        if on_device and not torch.is_grad_enabled():
+            return self._run_forward(history, target, history_region, target_region,
+                                     history_visit_rate, dist_mat, uid)
+        return self.restatement(history, target, history_region, target_region,
+                                history_visit_rate, dist_mat, uid)

@@ -585,7 +585,7 @@ class New1Trainer:
                  betas=(0.9, 0.999), eps=1e-8):
         from .model import New1
         from .new1 import _region_tensor, visit_rates
-        if not isinstance(model, New1):
+        if type(model) is not New1:   # New2 derives from New1: its geo term is not in this step
             raise NotImplementedError(f"New1Trainer: {type(model).__name__} is not New1")
         dev = model._check_device()
         if int(num_ng) < 1:

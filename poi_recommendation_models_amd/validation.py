@@ -172,6 +172,27 @@ def New1_validation(model, args, num_users, test_positive, val_positive, train_m
     return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
 
 
+def New2_validation(model, args, num_users, test_positive, val_positive, train_matrix,
+                    businessRegionEmbedList, poi_coos, k_list):
+    """The inline evaluation loop of run_new.py:551-570 (New2; the reference has no function for
+    it): per user the args.topk best POIs outside its training history, the batch being the
+    user's whole complement in ascending POI id as testDataset2.__getitem__ builds it
+    (run_new.py:242-264). `poi_coos` [P, 2] are the (lat, lng) the reference passes to
+    haversine_vector; the distances are evaluated per pair on the device (`new2.score_topk`), so
+    the reference's dense P x P float64 matrix is never built. A user with fewer than args.topk
+    candidates raises RuntimeError, as the reference's torch.topk does. Single-process only."""
+    import numpy as np
+    from .new2 import score_topk as new2_topk
+    model.eval()                                               # run_new.py:533
+    shape = train_matrix.shape
+    hist_len = np.diff(train_matrix.tocsr().indptr)[:num_users]
+    if np.any(shape[1] - hist_len < args.topk):
+        raise RuntimeError("selected index k out of range")   # torch.topk's error
+    ids, _ = new2_topk(model, train_matrix, businessRegionEmbedList, range(num_users), args.topk,
+                       coords=poi_coos)
+    return _metrics(test_positive, val_positive, ids.cpu().numpy(), k_list)
+
+
 def new4_validation(model, args, num_users, test_positive, val_positive, train_matrix,
                     businessRegionEmbedList, k_list, nearPOI, distributed=None):
     """validation.py:254-280 (New4): the context tables are built once (the reference rebuilds
